@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the point-trajectory hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A *step* is one pass of the hot path over one synthetic sequence: BASELINE.json configs[1] =
 100 x (1920x1080) forward/backward flow pairs, sample_ratio=2, chaining + occlusion only, i.e.
@@ -12,10 +12,15 @@ metric  = trajectory points per second (sum over all trajectories of their lengt
 N > 1   = N independent sequences, one per rank/GPU (sequences are the unit the reference's driver
           loops over, run_particlesfm.py:168-176); no data-path collective, weak scaling.
 
-Rank 0 prints ONE JSON line, kept under 4 KB (tests/test_bench_line.py): the contract's keys, `roofline` of the
-flow-chaining kernel (HIP events on the launch stream, inside the timed region), `cpu_baseline` (the CPU oracle on a
-bounded sample of the same workload), `parity`, and `extras` = a few numbers per figure measured outside the timed
-region.  The full records of those figures (bench_extras.py) go to bench_extras.json, never into the line.
+A plain run sets up, warms up, times the K steps and prints ONE JSON line with the contract's keys (`metric`, `value`,
+`unit`, `ms_per_step`, ...).  --dump-outputs DIR also writes what the last timed step computed as DIR/<name>.npy
+(dump_outputs below).
+
+--full adds everything else, as one line kept under 4 KB (tests/test_bench_line.py): `roofline` of the flow-chaining
+kernel (HIP events on the launch stream, inside the timed region), `kernels` (the other ways of running the step, timed
+after it), `cpu_baseline` (the CPU oracle on a bounded sample of the same workload), `parity`, and `extras` = a few
+numbers per figure measured outside the timed region.  The full records of those figures (bench_extras.py) go to
+bench_extras.json, never into the line.  With N > 1 the one-sequence-over-all-ranks figures are --full only as well.
 """
 import argparse
 import json
@@ -26,6 +31,10 @@ import time
 from bench_common import (ROOT, H, W, N_FRAMES, RATIO, THRES, HBM_PEAK_GBS, quiet_gc, source_sha16, replayed, cpu_baseline)
 
 LINE_LIMIT = 4096     # bytes of the one JSON line (the round-5 line was 33 KB and the driver could not parse it)
+# --dump-outputs: at most this many trajectories (birth, length) and points (positions) are written; beyond that a fixed, seeded
+# sample.  2^21 x 8 B x 2 + 2^20 x 16 B = 48 MiB at most (the headline sequence: 2.07 M trajectories, all of them; 51.6 M points)
+DUMP_MAX_TRAJ = 1 << 21
+DUMP_MAX_POINTS = 1 << 20
 
 
 def _round(v, sig=6):
@@ -75,6 +84,38 @@ def write_full(record):
     return wrote
 
 
+def _dump_sample(n, cap, seed):
+    """All of range(n), or `cap` sorted indices of it drawn with a fixed seed."""
+    import numpy as np
+    if n <= cap:
+        return slice(None)
+    return np.sort(np.random.default_rng(seed).choice(n, cap, replace=False))
+
+
+def dump_outputs(out_dir, ctx, info):
+    """What a caller of the timed path receives (trajectory.py::_result_to_host of the result the last step left in HBM): per
+    trajectory its birth frame and length, in id order, and the positions of its points.  Written as float64 .npy files:
+      counts.npy    [n_traj, n_points]
+      birth.npy     (n,) birth frame of trajectory traj_index[k]
+      length.npy    (n,) its number of points
+      xy.npy        (m, 2) positions of points point_index[k] of the id-ordered CSR (all points in CSR order if not sampled)
+    Beyond DUMP_MAX_TRAJ trajectories / DUMP_MAX_POINTS points, traj_index / point_index are a sorted sample drawn with a fixed
+    seed from the counts alone (_dump_sample), so equal counts give equal indices on every run and every build."""
+    import numpy as np
+    from point_trajectory.trajectory import _result_to_host
+    R = _result_to_host(ctx, info)
+    n_traj, n_pts = int(R.birth.shape[0]), int(R.xy.shape[0])
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"counts": np.array([n_traj, n_pts], np.float64)}
+    ti = _dump_sample(n_traj, DUMP_MAX_TRAJ, 1)
+    pi = _dump_sample(n_pts, DUMP_MAX_POINTS, 2)
+    arrays["birth"] = R.birth[ti].astype(np.float64)
+    arrays["length"] = R.length[ti].astype(np.float64)
+    arrays["xy"] = np.ascontiguousarray(R.xy[pi], dtype=np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -89,6 +130,12 @@ def main():
     ap.add_argument("--no-extras", action="store_true",
                     help="only warm-up + timed steps (what profiles/*_kernel_stats.csv is collected with): skips the figures "
                          "measured outside the timed region (overlapped psfm_connect, track_optimize, concurrent sequences)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure: roofline, the other ways of running the "
+                         "step, the CPU baseline and parity, bench_extras.py's figures (-> bench_extras.json), and with --gpus N > 1 "
+                         "one sequence over all ranks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0's sequence) as DIR/<name>.npy, float64, < 64 MB")
     args = ap.parse_args()
 
     if args.gpus > 1 and "RANK" not in os.environ:
@@ -185,6 +232,8 @@ def main():
     dt = time.perf_counter() - t0
     prof = ctx.profile()
     ctx.set_profiling(False)
+    if args.dump_outputs and rank == 0:     # before anything else runs on the context: its result is the last timed step's
+        dump_outputs(args.dump_outputs, ctx, info)
     # ---- the other ways of running the same step, outside the timed region ----
     def timed(fn, mode, prof_stride):
         ctx.set_chain_mode(mode)
@@ -202,7 +251,7 @@ def main():
         assert int(inf.n_points) == int(info.n_points) and int(inf.n_traj) == int(info.n_traj)
         return ms, pr, inf
     variants = None
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         us = lambda pr, k: 1e3 * pr[k]["total_ms"] / max(pr[k]["launches"], 1)
         ms2, pr2, inf2 = timed(step_two_calls, 0, 1)       # flow_check kernel, then the persistent loop on its maps
         ms1, pr1, inf1 = timed(step, 1, 8)                 # psfm_connect with one chain_step launch per frame
@@ -233,7 +282,7 @@ def main():
 
     # ---- ONE sequence over all ranks (exact track-sharded mode), outside the timed region ----
     single, single_hard, hung = None, None, False
-    if world > 1:      # (world size 1: bench_extras.run_all times the same two figures, inside its budget)
+    if world > 1 and args.full:      # (world size 1: bench_extras.run_all times the same two figures, inside its budget)
         # configs[3], and the headline shape on flows whose solves reject steps (psfm_synth.HARD: the redo path of the sharded engine) --
         # each rank's share in a child process: a device fault in a cross-GPU form must not take the headline figure with it
         dist.barrier()
@@ -241,41 +290,6 @@ def main():
         single, single_hard = res if isinstance(res, tuple) else (res, None)      # (a dict = guarded()'s own error record)
 
     if rank == 0:
-        # ---- roofline of the flow-chaining kernel (K2): algorithmic bytes per launch / avg duration ----
-        # chain_step/frame = min(8P,32A) + min(P,4A) + 16A + 16A + A, A = tracks alive at the step.
-        import ctypes
-        birth = np.empty(int(info.n_traj), np.int32)
-        length = np.empty(int(info.n_traj), np.int32)
-        _hip.check(_hip.lib().psfm_result_copy(ctx.handle, birth.ctypes.data_as(ctypes.c_void_p),
-                                               length.ctypes.data_as(ctypes.c_void_p), None, None,
-                                               _hip.current_stream_ptr()))
-        last = birth.astype(np.int64) + length - 1
-        alive_steps = float(points - int((last == n_flows).sum()))   # sum_t A_t over the n_flows launches
-        A = alive_steps / n_flows
-        P = float(H * W)
-        chain_bytes = min(8 * P, 32 * A) + min(P, 4 * A) + 16 * A + 16 * A + A
-        ch = prof["chain_step"]
-        chain_us = 1e3 * ch["total_ms"] / max(ch["launches"], 1)
-        persistent = int(info.chain_mode) == 2
-        fused = persistent and prof["flow_check"]["launches"] == 0    # no stand-alone flow_check ran: it is in the loop
-        frame_bytes = chain_bytes
-        fc_step_bytes = 17.0 * P
-        if persistent:
-            # ONE launch runs all n_flows steps (psfm_chain_persist_kernel): algorithmic bytes per launch = the per-step
-            # figure x n_flows -- the positions it keeps in registers between steps are still counted as read.  When
-            # psfm_connect fuses flow_check into the loop, that kernel also moves flow_check's 17P bytes per step.
-            frame_bytes = chain_bytes + (fc_step_bytes if fused else 0.0)
-            chain_bytes = frame_bytes * n_flows
-        achieved = chain_bytes / (chain_us * 1e-6) / 1e9 if chain_us > 0 else 0.0
-        tfile = os.path.join(ROOT, "profiles", ("traffic_chain_fused.json" if fused else "traffic_chain_persist.json")
-                             if persistent else "traffic_chain_step.json")
-        tv, tprov = replayed(tfile)
-        traffic = tv.get("hbm_bytes_per_launch") if tv else None
-        fc = prof["flow_check"]
-        fc_us = 1e3 * fc["total_ms"] / max(fc["launches"], 1)
-        fc_bytes = 17.0 * P * n_flows
-        if fused and variants:    # the stand-alone kernel, from the two-call variant
-            fc_us = variants["two_calls_flow_check_then_track"]["flow_check_launch_us"]
         sha = source_sha16()
         out = {
             "metric": "trajectory-points/s", "value": total_points * args.steps / dt_max,
@@ -288,75 +302,112 @@ def main():
                        "flow_check_thres": THRES, "points_per_sequence": points, "trajectories": int(info.n_traj),
                        "parallelism": "sequence-per-gpu x%d" % world, "world_size": dist.get_world_size() if world > 1 else 1,
                        "source_sha16": sha},
-            "roofline": {"bound": "hbm",
-                         "kernel": ("psfm_chain_persist_kernel (flow_check fused in)" if fused else "psfm_chain_persist_kernel")
-                         if persistent else "psfm_chain_step_kernel",
-                         "achieved": achieved,
-                         "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                         # physical HBM bytes of the same launch (fabric-side PMC counters, separate passes, replayed from profiles/) and
-                         # the fraction of the peak THEY amount to
-                         "traffic": traffic,
-                         "frac_physical": (traffic / (chain_us * 1e-6) / 1e9 / HBM_PEAK_GBS) if (traffic and chain_us > 0) else None,
-                         "traffic_file": tprov["file"] if tprov else None,
-                         "traffic_same_sources": tprov["same_sources"] if tprov else None,
-                         "bytes_per_launch": chain_bytes, "avg_launch_us": chain_us,
-                         "steps_per_launch": n_flows if persistent else 1,
-                         "bytes_per_step": frame_bytes,
-                         "chain_step_bytes_per_step": frame_bytes - (fc_step_bytes if fused else 0.0),
-                         "avg_alive_tracks": A},
-            "kernels": {"flow_check_alone_us": fc_us,
-                        "flow_check_alone_frac": fc_bytes / (fc_us * 1e-6) / 1e9 / HBM_PEAK_GBS if fc_us > 0 else None,
-                        "finalize_avg_us": 1e3 * prof["finalize"]["total_ms"] / max(prof["finalize"]["launches"], 1)},
         }
-        if variants:
-            v2 = variants["two_calls_flow_check_then_track"]
-            out["kernels"]["chain_alone_us_per_step"] = v2["chain_us_per_step"]
-            out["kernels"]["chain_alone_frac"] = (frame_bytes - (fc_step_bytes if fused else 0.0)) / (v2["chain_us_per_step"] * 1e-6) / 1e9 / HBM_PEAK_GBS \
-                if v2["chain_us_per_step"] > 0 else None
-            out["kernels"]["two_calls_ms_per_step"] = v2["ms_per_step"]
-            out["kernels"]["per_frame_launches_ms_per_step"] = variants["per_frame_launches_overlapped"]["ms_per_step"]
         if world > 1:
             out["config"]["backend"] = rank_info["backend"]
             out["config"]["rccl_version"] = rank_info["rccl_version"]
             out["config"]["points_per_rank"] = [r["points"] for r in rank_info["per_rank"]]
         if dryrun:
             out["dryrun"] = "%d ranks on ONE GPU over gloo: the multi-rank control flow only, NOT a measurement" % world
-        full = {"headline": None, "ranks": rank_info, "variants": variants, "traffic_source": tprov}
-        if single is not None:
-            full["single_sequence"] = single
-        if single_hard is not None:
-            full["single_sequence_hard"] = single_hard
-        if world == 1 and not args.no_cpu:
-            n_cpu = min(args.cpu_pairs, n_flows)
-            cb, Rc = cpu_baseline(flows_f, flows_b, n_cpu)
-            full["cpu_baseline"] = cb
-            refc = cb.get("reference_python_build_container") or {}
-            out["cpu_baseline"] = {"value": cb["value"], "unit": cb["unit"], "cores": cb["cores"], "kind": cb["kind"],
-                                   "host_cores": cb["host_cores"],
-                                   "sample": "%d of %d frame pairs of this workload (flow_check + track + id order), C restatement of the reference path, "
-                                             "%d OpenMP threads" % (n_cpu, n_flows, cb["cores"]),
-                                   "value_8_threads": cb["port_8_threads"]["value"],
-                                   # the unmodified reference Python: timed in the build container only (it cannot travel to this box)
-                                   "reference_python_points_per_s_build_container": refc.get("track_points_per_s")}
-            if n_cpu == n_flows:
-                # full-size parity, checked on the spot: ids / lengths bit-exact, positions bit-exact (track mode)
-                from point_trajectory.trajectory import _result_to_host
-                Rg = _result_to_host(ctx, info)
-                same = bool(Rg.birth.shape == Rc.birth.shape and np.array_equal(Rg.birth, Rc.birth)
-                            and np.array_equal(Rg.length, Rc.length))
-                out["parity"] = {"vs": "cpu oracle, whole workload", "ids_lengths_equal": same,
-                                 "max_abs_dxy_px": float(np.abs(Rg.xy - Rc.xy).max()) if same else None}
-                del Rg
-            del Rc
-        if world == 1 and not args.no_extras:
-            # every figure outside the timed region: bench_extras.py; the line carries a few numbers of each
-            import bench_extras
-            del flows_b, flows_f, d
-            torch.cuda.empty_cache()
-            full.update(bench_extras.run_all(ctx, dev, n_frames, budget_s=args.extras_budget))
-        out["extras"] = bench_extras_summary(full)
-        full["headline"] = dict(out)
-        out["extras_file"] = write_full(full)
+        if args.full:
+            # ---- everything beyond the headline figure: --full only ----
+            # ---- roofline of the flow-chaining kernel (K2): algorithmic bytes per launch / avg duration ----
+            # chain_step/frame = min(8P,32A) + min(P,4A) + 16A + 16A + A, A = tracks alive at the step.
+            import ctypes
+            birth = np.empty(int(info.n_traj), np.int32)
+            length = np.empty(int(info.n_traj), np.int32)
+            _hip.check(_hip.lib().psfm_result_copy(ctx.handle, birth.ctypes.data_as(ctypes.c_void_p),
+                                                   length.ctypes.data_as(ctypes.c_void_p), None, None,
+                                                   _hip.current_stream_ptr()))
+            last = birth.astype(np.int64) + length - 1
+            alive_steps = float(points - int((last == n_flows).sum()))   # sum_t A_t over the n_flows launches
+            A = alive_steps / n_flows
+            P = float(H * W)
+            chain_bytes = min(8 * P, 32 * A) + min(P, 4 * A) + 16 * A + 16 * A + A
+            ch = prof["chain_step"]
+            chain_us = 1e3 * ch["total_ms"] / max(ch["launches"], 1)
+            persistent = int(info.chain_mode) == 2
+            fused = persistent and prof["flow_check"]["launches"] == 0    # no stand-alone flow_check ran: it is in the loop
+            frame_bytes = chain_bytes
+            fc_step_bytes = 17.0 * P
+            if persistent:
+                # ONE launch runs all n_flows steps (psfm_chain_persist_kernel): algorithmic bytes per launch = the per-step
+                # figure x n_flows -- the positions it keeps in registers between steps are still counted as read.  When
+                # psfm_connect fuses flow_check into the loop, that kernel also moves flow_check's 17P bytes per step.
+                frame_bytes = chain_bytes + (fc_step_bytes if fused else 0.0)
+                chain_bytes = frame_bytes * n_flows
+            achieved = chain_bytes / (chain_us * 1e-6) / 1e9 if chain_us > 0 else 0.0
+            tfile = os.path.join(ROOT, "profiles", ("traffic_chain_fused.json" if fused else "traffic_chain_persist.json")
+                                 if persistent else "traffic_chain_step.json")
+            tv, tprov = replayed(tfile)
+            traffic = tv.get("hbm_bytes_per_launch") if tv else None
+            fc = prof["flow_check"]
+            fc_us = 1e3 * fc["total_ms"] / max(fc["launches"], 1)
+            fc_bytes = 17.0 * P * n_flows
+            if fused and variants:    # the stand-alone kernel, from the two-call variant
+                fc_us = variants["two_calls_flow_check_then_track"]["flow_check_launch_us"]
+            out["roofline"] = {"bound": "hbm",
+                               "kernel": ("psfm_chain_persist_kernel (flow_check fused in)" if fused else "psfm_chain_persist_kernel")
+                               if persistent else "psfm_chain_step_kernel",
+                               "achieved": achieved,
+                               "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                               # physical HBM bytes of the same launch (fabric-side PMC counters, separate passes, replayed from profiles/) and
+                               # the fraction of the peak THEY amount to
+                               "traffic": traffic,
+                               "frac_physical": (traffic / (chain_us * 1e-6) / 1e9 / HBM_PEAK_GBS) if (traffic and chain_us > 0) else None,
+                               "traffic_file": tprov["file"] if tprov else None,
+                               "traffic_same_sources": tprov["same_sources"] if tprov else None,
+                               "bytes_per_launch": chain_bytes, "avg_launch_us": chain_us,
+                               "steps_per_launch": n_flows if persistent else 1,
+                               "bytes_per_step": frame_bytes,
+                               "chain_step_bytes_per_step": frame_bytes - (fc_step_bytes if fused else 0.0),
+                               "avg_alive_tracks": A}
+            out["kernels"] = {"flow_check_alone_us": fc_us,
+                              "flow_check_alone_frac": fc_bytes / (fc_us * 1e-6) / 1e9 / HBM_PEAK_GBS if fc_us > 0 else None,
+                              "finalize_avg_us": 1e3 * prof["finalize"]["total_ms"] / max(prof["finalize"]["launches"], 1)}
+            if variants:
+                v2 = variants["two_calls_flow_check_then_track"]
+                out["kernels"]["chain_alone_us_per_step"] = v2["chain_us_per_step"]
+                out["kernels"]["chain_alone_frac"] = (frame_bytes - (fc_step_bytes if fused else 0.0)) / (v2["chain_us_per_step"] * 1e-6) / 1e9 / HBM_PEAK_GBS \
+                    if v2["chain_us_per_step"] > 0 else None
+                out["kernels"]["two_calls_ms_per_step"] = v2["ms_per_step"]
+                out["kernels"]["per_frame_launches_ms_per_step"] = variants["per_frame_launches_overlapped"]["ms_per_step"]
+            full = {"headline": None, "ranks": rank_info, "variants": variants, "traffic_source": tprov}
+            if single is not None:
+                full["single_sequence"] = single
+            if single_hard is not None:
+                full["single_sequence_hard"] = single_hard
+            if world == 1 and not args.no_cpu:
+                n_cpu = min(args.cpu_pairs, n_flows)
+                cb, Rc = cpu_baseline(flows_f, flows_b, n_cpu)
+                full["cpu_baseline"] = cb
+                refc = cb.get("reference_python_build_container") or {}
+                out["cpu_baseline"] = {"value": cb["value"], "unit": cb["unit"], "cores": cb["cores"], "kind": cb["kind"],
+                                       "host_cores": cb["host_cores"],
+                                       "sample": "%d of %d frame pairs of this workload (flow_check + track + id order), C restatement of the reference path, "
+                                                 "%d OpenMP threads" % (n_cpu, n_flows, cb["cores"]),
+                                       "value_8_threads": cb["port_8_threads"]["value"],
+                                       # the unmodified reference Python: replayed from BASELINE_MEASURED.json (its sources are not shipped here)
+                                       "reference_python_points_per_s_build_container": refc.get("track_points_per_s")}
+                if n_cpu == n_flows:
+                    # full-size parity, checked on the spot: ids / lengths bit-exact, positions bit-exact (track mode)
+                    from point_trajectory.trajectory import _result_to_host
+                    Rg = _result_to_host(ctx, info)
+                    same = bool(Rg.birth.shape == Rc.birth.shape and np.array_equal(Rg.birth, Rc.birth)
+                                and np.array_equal(Rg.length, Rc.length))
+                    out["parity"] = {"vs": "cpu oracle, whole workload", "ids_lengths_equal": same,
+                                     "max_abs_dxy_px": float(np.abs(Rg.xy - Rc.xy).max()) if same else None}
+                    del Rg
+                del Rc
+            if world == 1 and not args.no_extras:
+                # every figure outside the timed region: bench_extras.py; the line carries a few numbers of each
+                import bench_extras
+                del flows_b, flows_f, d
+                torch.cuda.empty_cache()
+                full.update(bench_extras.run_all(ctx, dev, n_frames, budget_s=args.extras_budget))
+            out["extras"] = bench_extras_summary(full)
+            full["headline"] = dict(out)
+            out["extras_file"] = write_full(full)
         print(compact_line(out), flush=True)
     if hung:            # a rank is stuck in a collective of the extra mode: the line is out, leave without the barrier
         sys.stdout.flush()

@@ -1,5 +1,5 @@
 """bench_extras.py -- everything bench.py measures OUTSIDE its timed region: the other BASELINE.json shapes, the path-consistency
-solver on three flow distributions, B sequences per launch, one sequence over all ranks, disk to disk.  bench.py runs `run_all`
+solver on three flow distributions, B sequences per launch, one sequence over all ranks, disk to disk.  bench.py --full runs `run_all`
 after the headline step unless --no-extras, writes the full record to bench_extras.json (beside bench.py and, when it exists,
 under gpurun_out/) and carries `summary()` of it -- a few numbers per figure -- in its one JSON line."""
 import json

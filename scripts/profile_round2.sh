@@ -3,6 +3,7 @@
 # kernel-trace stats first, then separate PMC passes (never --pmc together with other trace domains).
 # Usage (on the GPU box): bash scripts/profile_round2.sh r02_a      -> gpurun_out/r02_a/...
 TAG=${1:-r02}
+REPO=$(cd "$(dirname "$0")/.." && pwd)     # the repository root (this script is in scripts/)
 export TMPDIR=/tmp
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p $OUT
@@ -21,7 +22,7 @@ timeout 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE -f csv -d $OUT/opt_pmc_fet
 timeout 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE TCC_HIT_sum TCC_MISS_sum -f csv -d $OUT/opt_pmc_write -o w -- $O1 > $OUT/opt_pmc_write.log 2>&1 < /dev/null
 timeout 300 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_VMEM -f csv -d $OUT/opt_pmc_sq -o s -- $O1 > $OUT/opt_pmc_sq.log 2>&1 < /dev/null
 fi   # PSFM_PROFILE_HEADLINE_ONLY=1: only the headline step (the track_optimize kernels did not change)
-timeout 500 python $GRAFT_REPO_ROOT/bench.py --steps 10 --warmup 2 > $OUT/bench.json 2> $OUT/bench.err < /dev/null
+timeout 500 python "$REPO/bench.py" --full --steps 10 --warmup 2 > $OUT/bench.json 2> $OUT/bench.err < /dev/null
 
 
 

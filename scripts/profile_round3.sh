@@ -3,6 +3,7 @@
 # kernel-trace stats first, then separate PMC passes (never --pmc together with other trace domains).
 # Usage (on the GPU box): bash scripts/profile_round2.sh r03_a      -> gpurun_out/r03_a/...
 TAG=${1:-r03}
+REPO=$(cd "$(dirname "$0")/.." && pwd)     # the repository root (this script is in scripts/)
 export TMPDIR=/tmp
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p $OUT
@@ -23,7 +24,7 @@ timeout 300 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLE
 # the hard distribution (sigma 0.3, 5 % occluders): every solve through the launch chain / the persistent solve
 timeout 300 env PSFM_PROBE_HARD=1 PSFM_PROBE_MODES=adaptive rocprofv3 --kernel-trace --stats -f csv -d $OUT/hard_stats -o ${TAG}_hard -- python $GRAFT_REPO_ROOT/scripts/probe_solver.py > $OUT/hard_under_rocprof.log 2>&1 < /dev/null
 fi   # PSFM_PROFILE_HEADLINE_ONLY=1: only the headline step (the track_optimize kernels did not change)
-timeout 500 python $GRAFT_REPO_ROOT/bench.py --steps 10 --warmup 2 > $OUT/bench.json 2> $OUT/bench.err < /dev/null
+timeout 500 python "$REPO/bench.py" --full --steps 10 --warmup 2 > $OUT/bench.json 2> $OUT/bench.err < /dev/null
 
 
 

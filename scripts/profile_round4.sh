@@ -5,6 +5,7 @@
 # (kernel stats, PMC summaries, profiles/traffic_chain_*.json and profiles/solver_valu.json stamped with the source hash).
 # Usage (on the GPU box): bash scripts/profile_round4.sh r04_x      -> gpurun_out/r04_x_summary/
 TAG=${1:-r04}
+REPO=$(cd "$(dirname "$0")/.." && pwd)     # the repository root (this script is in scripts/)
 export TMPDIR=/tmp
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p $OUT
@@ -46,6 +47,6 @@ run hard_stats --stats -f csv -d $OUT/hard_stats -o ${TAG}_hard -- $PR
 run hard_pmc_sq --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_TRANS_F64 --kernel-include-regex "psfm_pc_" -f csv -d $OUT/hard_pmc_sq -o s -- $PR
 unset PSFM_PROBE_HARD PSFM_PROBE_MODES
 # ---- the default bench line of this binary ----
-timeout 900 python $GRAFT_REPO_ROOT/bench.py --steps 10 --warmup 2 > $OUT/bench.json 2> $OUT/bench.err < /dev/null
+timeout 900 python "$REPO/bench.py" --full --steps 10 --warmup 2 > $OUT/bench.json 2> $OUT/bench.err < /dev/null
 python $GRAFT_REPO_ROOT/scripts/summarize_profiles4.py $TAG
 ls $GRAFT_REPO_ROOT/gpurun_out/${TAG}_summary

@@ -5,6 +5,7 @@
 # scripts/summarize_profiles5.py boils it down on the box.  Never --pmc together with other trace domains.
 # Usage (on the GPU box): bash scripts/profile_round5.sh r05_x      -> gpurun_out/r05_x_summary/
 TAG=${1:-r05}
+REPO=$(cd "$(dirname "$0")/.." && pwd)     # the repository root (this script is in scripts/)
 export TMPDIR=/tmp
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p $OUT
@@ -56,5 +57,5 @@ SUM=$GRAFT_REPO_ROOT/gpurun_out/${TAG}_summary
 for f in traffic_chain_fused.json traffic_chain_persist.json traffic_chain_step.json solver_valu.json batch_pmc.json; do
   [ -f $SUM/$f ] && cp $SUM/$f $GRAFT_REPO_ROOT/profiles/$f
 done
-timeout 1200 python $GRAFT_REPO_ROOT/bench.py --steps 20 --warmup 5 > $SUM/${TAG}_bench.json 2> $SUM/${TAG}_bench.err < /dev/null
+timeout 1200 python "$REPO/bench.py" --full --steps 20 --warmup 5 > $SUM/${TAG}_bench.json 2> $SUM/${TAG}_bench.err < /dev/null
 ls $SUM

@@ -75,3 +75,34 @@ def test_main_prints_the_line_last():
     src = open(os.path.join(ROOT, "bench.py")).read()
     assert src.count("print(compact_line(out), flush=True)") == 1      # the only print of main(): the last stdout line is the JSON
     assert "print(json.dumps(" not in src
+
+
+def test_dump_outputs_is_float_bounded_and_its_sample_is_fixed(tmp_path, monkeypatch):
+    """--dump-outputs: what the caller of the timed path receives (birth, length, positions) as float .npy files, at most 64 MB
+    for a result of the headline size, and the same files for the same result on every run."""
+    import numpy as np
+    from point_trajectory import trajectory
+
+    class Result:
+        pass
+
+    def fake_result(ctx, info):
+        rng = np.random.default_rng(3)
+        r = Result()
+        r.length = rng.integers(1, 50, bench.DUMP_MAX_TRAJ + 1000).astype(np.int32)
+        r.birth = rng.integers(0, 100, r.length.shape[0]).astype(np.int32)
+        r.xy = rng.normal(size=(int(r.length.sum()), 2))
+        return r
+    monkeypatch.setattr(trajectory, "_result_to_host", fake_result)
+    R = fake_result(None, None)
+    files = {}
+    for run in ("a", "b"):
+        names = bench.dump_outputs(str(tmp_path / run), None, None)
+        files[run] = {n: np.load(str(tmp_path / run / (n + ".npy"))) for n in names}
+        assert sum(os.path.getsize(str(tmp_path / run / (n + ".npy"))) for n in names) <= 64 << 20
+    for n, a in files["a"].items():
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, files["b"][n])
+    assert files["a"]["counts"].tolist() == [R.birth.shape[0], R.xy.shape[0]]
+    assert files["a"]["birth"].shape == (bench.DUMP_MAX_TRAJ,) and files["a"]["xy"].shape == (bench.DUMP_MAX_POINTS, 2)
+    # the sampled entries are the result's own: each sampled position occurs in it
+    assert np.isin(files["a"]["xy"][:100, 0], R.xy[:, 0]).all()

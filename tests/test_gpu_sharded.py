@@ -292,7 +292,7 @@ def test_bench_multi_rank_control_flow_dry_run_on_one_gpu():
     env = dict(os.environ)
     env["PSFM_BENCH_DRYRUN_ONE_GPU"] = "1"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--frames", "11",
-                        "--single-seq-frames", "13"], capture_output=True, text=True, env=env, timeout=600)
+                        "--single-seq-frames", "13", "--full"], capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     assert r.stdout.strip().splitlines()[-1].startswith("{") and len(r.stdout.strip().splitlines()[-1]) < 4096
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -318,7 +318,7 @@ def test_bench_headline_survives_a_rank_dying_in_the_one_sequence_mode():
     env = dict(os.environ)
     env.update(PSFM_BENCH_DRYRUN_ONE_GPU="1", PSFM_BENCH_CHILD_ABORT="1", PSFM_BENCH_CHILD_TIMEOUT="120")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--frames", "11",
-                        "--single-seq-frames", "13"], capture_output=True, text=True, env=env, timeout=600)
+                        "--single-seq-frames", "13", "--full"], capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 2 and line["value"] > 0 and "roofline" in line

@@ -212,23 +212,16 @@ def test_second_restatement_agrees_on_failure_and_trivial_cases():
 def test_reference_python_with_the_second_restatement_as_solver():
     """The reference's own track_optimize (track_optimize.py:24-53, trajectory.py:161-194), unmodified, with the NumPy
     restatement as `particlesfm.optimize_location`, against the C oracle's whole-sequence result: ids / lengths equal,
-    positions within 1e-9 px.  (The committed opt_* fixtures were produced with the C restatement in that seat.)"""
-    from oracle import ref_shim
-    from oracle import ceres_tr_numpy as ct
-    if not ref_shim.available():
-        pytest.skip("reference tree not present")
-    ref = ref_shim.load_reference(optimize_location=lambda *a: ct.optimize_location(*a)[0])
-    d = psfm_synth.synth_sequence(7, 60, 84, seed=91, sigma=0.25, n_occluders=2, stride2=True)
+    positions within 1e-9 px.  (The committed opt_* fixtures were produced with the C restatement in that seat.)  The
+    reference's result is recorded in tests/golden/refpy_opt_ct_60x84_r2.npz (tests/golden/make_reference_runs_golden.py)."""
+    g = golden("refpy_opt_ct_60x84_r2")
+    d = regen_inputs(g, stride2=True)
     _, occ = orc.flow_check(d["flows_f"], d["flows_b"], 1.0)
     _, occ2 = orc.flow_check(d["flows_f2"], d["flows_b2"], 1.0)
-    O = orc.track_optimize(d["flows_f"], d["flows_f2"], occ, occ2, 2)
-    import warnings
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        full = ref.track_optimize(d["flows_f"], d["flows_f2"], occ, occ2, 2)
-    birth, length, off, xy = ref_shim.trajs_to_csr(full)
-    assert np.array_equal(birth, O.birth) and np.array_equal(length, O.length)
-    assert float(np.abs(xy - O.xy).max()) <= 1e-9
+    O = orc.track_optimize(d["flows_f"], d["flows_f2"], occ, occ2, int(g["ratio"]))
+    assert np.array_equal(g["birth"], O.birth) and np.array_equal(g["length"], O.length)
+    assert np.array_equal(g["off"], O.off)
+    assert float(np.abs(g["xy"] - O.xy).max()) <= 1e-9
 
 
 def test_ceres_assumption_switches_are_mirrored_in_both_restatements():
