@@ -66,7 +66,7 @@ __device__ __forceinline__ unsigned long long ps_match8(unsigned d)
 #endif
 #define PS_HBLOCK (PS_GROUP * PS_HWAVES * PSFM_WAVE)
 #define PS_HITEMS (PS_TILE / (PS_HWAVES * PSFM_WAVE))
-__global__ __launch_bounds__(PS_HBLOCK) void psfm_sort_hist_kernel(const unsigned* __restrict__ keys, int64_t n, int shift,
+__global__ __launch_bounds__(PS_HBLOCK) void psfm_sort_hist_kernel(const unsigned* __restrict__ keys, int64_t n, int shift, unsigned dmask,
                                                                    unsigned* __restrict__ cnt, unsigned* __restrict__ grp, int nb)
 {
     __shared__ unsigned s_h[PS_GROUP][PS_HREP][PS_DIGITS];
@@ -94,7 +94,7 @@ __global__ __launch_bounds__(PS_HBLOCK) void psfm_sort_hist_kernel(const unsigne
         // first and adding once per digit -- the scatter kernel's way -- is 65 instructions per key on the quarter of the CUs this
         // launch occupies.)
         const bool ok = off < nv;
-        const unsigned d = (k[i] >> shift) & 255u;
+        const unsigned d = (k[i] >> shift) & dmask;
         const unsigned long long valid = __ballot(ok);
         const unsigned d0 = (unsigned)__builtin_amdgcn_readfirstlane((int)d);
         if (__ballot(ok && d == d0) == valid) {
@@ -127,7 +127,7 @@ __global__ __launch_bounds__(PS_HBLOCK) void psfm_sort_hist_kernel(const unsigne
 #define PS_CROUNDS (PS_ITEMS / PS_CHAINS)
 __global__ __launch_bounds__(PS_BLOCK) void psfm_sort_scatter_kernel(const unsigned* __restrict__ kin, const int* __restrict__ vin,
                                                                      unsigned* __restrict__ kout, int* __restrict__ vout, int64_t n,
-                                                                     int shift, const unsigned* __restrict__ cnt,
+                                                                     int shift, unsigned dmask, const unsigned* __restrict__ cnt,
                                                                      const unsigned* __restrict__ grp, int ngrp)
 {
     __shared__ unsigned s_k[PS_TILE];
@@ -149,7 +149,7 @@ __global__ __launch_bounds__(PS_BLOCK) void psfm_sort_scatter_kernel(const unsig
     for (int i = 0; i < PS_ITEMS; ++i) {
         const int off = wave * PS_WSPAN + i * PSFM_WAVE + lane;
         const bool ok = off < nv;
-        k[i] = ok ? kin[tile0 + off] : 0xffffffffu;      // padding: digit 255 in every pass, behind every key of the tile
+        k[i] = ok ? kin[tile0 + off] : 0xffffffffu;      // padding: the largest digit in every pass, behind every key of the tile
         v[i] = ok ? vin[tile0 + off] : 0;
     }
     // digit `tid` of the tiles in front of this one (whole groups; the tiles of its own group: H left that prefix in the tile's row),
@@ -177,8 +177,8 @@ __global__ __launch_bounds__(PS_BLOCK) void psfm_sort_scatter_kernel(const unsig
             unsigned long long peers[PS_CHAINS];
 #pragma unroll
             for (int ch = 0; ch < PS_CHAINS; ++ch) {
-                if (PS_WHATIF & 2) k[ch * PS_CROUNDS + i] &= ~(255u << shift);      // (everything digit 0; only with 4: no stores)
-                d[ch] = (k[ch * PS_CROUNDS + i] >> shift) & 255u;
+                if (PS_WHATIF & 2) k[ch * PS_CROUNDS + i] &= ~(dmask << shift);      // (everything digit 0; only with 4: no stores)
+                d[ch] = (k[ch * PS_CROUNDS + i] >> shift) & dmask;
                 peers[ch] = (PS_WHATIF & 2) ? ~0ull : ps_match8(d[ch]);
             }
             // every lane reads its digit's counter, the first of the peers writes it back: plain LDS accesses -- the wave runs them in
@@ -227,7 +227,7 @@ __global__ __launch_bounds__(PS_BLOCK) void psfm_sort_scatter_kernel(const unsig
     __syncthreads();
 #pragma unroll
     for (int i = 0; i < PS_ITEMS; ++i) {
-        const unsigned d = (k[i] >> shift) & 255u;
+        const unsigned d = (k[i] >> shift) & dmask;
         const unsigned q = s_wc[wave][i / PS_CROUNDS][d] + r[i];
         s_k[q] = k[i];
         s_v[q] = v[i];
@@ -238,7 +238,7 @@ __global__ __launch_bounds__(PS_BLOCK) void psfm_sort_scatter_kernel(const unsig
         const int q = j * PS_BLOCK + tid;
         if (q < nv) {
             const unsigned key = s_k[q];
-            const int64_t pos = (int64_t)s_delta[(key >> shift) & 255u] + q;
+            const int64_t pos = (int64_t)s_delta[(key >> shift) & dmask] + q;
             if (PS_WHATIF & 4) { if (key == 0x12345u && pos == 77) kout[0] = key; continue; }
             kout[pos] = key;
             vout[pos] = s_v[q];
@@ -269,9 +269,12 @@ psfm_status psfm_sort_pairs32(psfm_ctx* c, unsigned* k_half0, int* v_half0, unsi
     unsigned* kout = (passes & 1) ? k_half0 : k_half1;
     int* vout = (passes & 1) ? v_half0 : v_half1;
     for (int p = 0; p < passes; ++p) {
-        hipLaunchKernelGGL(psfm_sort_hist_kernel, dim3((unsigned)ngrp), dim3(PS_HBLOCK), 0, s, (const unsigned*)kin, n, 8 * p, cnt, grp, (int)nb);
+        // the last pass of an end_bit that is no multiple of 8 takes only the digit's bits below end_bit: the bits above are not part of the key
+        const unsigned rest = end_bit - 8u * (unsigned)p;
+        const unsigned dmask = rest >= 8u ? 255u : (1u << rest) - 1u;
+        hipLaunchKernelGGL(psfm_sort_hist_kernel, dim3((unsigned)ngrp), dim3(PS_HBLOCK), 0, s, (const unsigned*)kin, n, 8 * p, dmask, cnt, grp, (int)nb);
         hipLaunchKernelGGL(psfm_sort_scatter_kernel, dim3((unsigned)nb), dim3(PS_BLOCK), 0, s, (const unsigned*)kin, (const int*)vin, kout,
-                           vout, n, 8 * p, (const unsigned*)cnt, (const unsigned*)grp, (int)ngrp);
+                           vout, n, 8 * p, dmask, (const unsigned*)cnt, (const unsigned*)grp, (int)ngrp);
         unsigned* tk = kin; kin = kout; kout = tk;
         int* tv = vin; vin = vout; vout = tv;
     }

@@ -82,3 +82,59 @@ SOLVER_BATCHES = [
     (270, 480, 100000, 4, 0.05, False),
     (33, 47, 1, 5, 0.1, False),         # a single track
 ]
+
+
+def _pairs_in_dict_order(datas, names):
+    """[(src image, tgt image, rows)] in the order the reference's dicts hold them (image order, then first use)."""
+    out = []
+    for i, n in enumerate(names):
+        for key, rows in datas[n].match_pairs.items():
+            a, b = key.split("-")
+            out.append((names.index(a), names.index(b), np.asarray(rows, np.int32).reshape(-1, 2)))
+    return out
+
+
+def check_match_tables(datas, names, g):
+    """traj_to_matches' output against tables in the layout of tests/golden/matches_*.npz: keypoints per image and their coordinates,
+    per image the pairs in dict order, the rows of each pair in loop order."""
+    kp = [np.asarray(datas[n].keypoints, np.float64).reshape(-1, 2) for n in names]
+    assert np.array_equal(np.cumsum([0] + [len(k) for k in kp]), g["kp_off"])
+    assert np.array_equal(np.concatenate(kp, 0), g["kp_xy"])
+    pairs = _pairs_in_dict_order(datas, names)
+    assert [p[0] for p in pairs] == g["pair_src"].tolist() and [p[1] for p in pairs] == g["pair_tgt"].tolist()
+    assert np.array_equal(np.cumsum([0] + [len(p[2]) for p in pairs]), g["pair_off"])
+    assert np.array_equal(np.concatenate([p[2] for p in pairs] or [np.zeros((0, 2), np.int32)], 0), g["rows"])
+
+
+def reference_sample_inside_window(trajs, frame_ids, min_length):
+    """Plain restatement of trajectory_base.cpp:115-185 (map-of-maps + loops), without the random shrink."""
+    inv = {}
+    for tid, (times, xy) in trajs.items():
+        for i, f in enumerate(times):
+            inv.setdefault(f, {})[tid] = i
+    counter = {}
+    for f in frame_ids:
+        for tid in inv.get(f, {}):
+            counter[tid] = counter.get(tid, 0) + 1
+    ids = [t for t in sorted(counter) if counter[t] >= min_length]
+    K, L = len(ids), len(frame_ids)
+    X, Y, M = np.zeros((K, L)), np.zeros((K, L)), np.zeros((K, L), np.int32)
+    for a, tid in enumerate(ids):
+        for b, f in enumerate(frame_ids):
+            if f in inv and tid in inv[f]:
+                X[a, b], Y[a, b] = trajs[tid][1][inv[f][tid]]
+                M[a, b] = 1
+    return ids, X, Y, M
+
+
+def reference_sample_window(birth, length, off, xy, f0, n_frames, min_length, traj_min_len, raw_hw, input_size):
+    """One window of motion_seg/load_cut_seq.py:60-89 from a full trajectory list (CSR): the saved set (length >= traj_min_len, ids =
+    list indices), sample_inside_window on frames [f0, f0 + n_frames), then data_utils.py:74-89 (resize: x /= raw_w / in_w, then
+    normalise: x /= in_w, clip to [0, 1]; y likewise).  Returns ids (K,), raw (K,L,2), normalised (K,L,2), absence mask (K,L,1)."""
+    trajs = {i: (list(range(int(birth[i]), int(birth[i]) + int(length[i]))), xy[off[i]:off[i + 1]])
+             for i in range(len(birth)) if length[i] >= traj_min_len}
+    ids, X, Y, M = reference_sample_inside_window(trajs, list(range(f0, f0 + n_frames)), min_length)
+    raw = np.stack([X, Y], -1)
+    ratio_h, ratio_w = float(raw_hw[0]) / float(input_size[0]), float(raw_hw[1]) / float(input_size[1])
+    nor = np.stack([(X / ratio_w) / input_size[1], (Y / ratio_h) / input_size[0]], -1)
+    return np.array(ids, np.int64), raw, np.clip(nor, 0.0, 1.0), (1 - M).astype(np.float64)[..., None]

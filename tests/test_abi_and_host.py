@@ -11,6 +11,8 @@ import sys
 import numpy as np
 import pytest
 
+from _common import reference_sample_inside_window
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -167,27 +169,6 @@ def test_track_npy_roundtrip_and_consumers(tmp_path):
     assert len(out["traj_ids"]) == 2
 
 
-def _reference_sample_inside_window(trajs, frame_ids, min_length):
-    """Plain restatement of trajectory_base.cpp:115-185 (map-of-maps + loops), without the random shrink."""
-    inv = {}
-    for tid, (times, xy) in trajs.items():
-        for i, f in enumerate(times):
-            inv.setdefault(f, {})[tid] = i
-    counter = {}
-    for f in frame_ids:
-        for tid in inv.get(f, {}):
-            counter[tid] = counter.get(tid, 0) + 1
-    ids = [t for t in sorted(counter) if counter[t] >= min_length]
-    K, L = len(ids), len(frame_ids)
-    X, Y, M = np.zeros((K, L)), np.zeros((K, L)), np.zeros((K, L), np.int32)
-    for a, tid in enumerate(ids):
-        for b, f in enumerate(frame_ids):
-            if f in inv and tid in inv[f]:
-                X[a, b], Y[a, b] = trajs[tid][1][inv[f][tid]]
-                M[a, b] = 1
-    return ids, X, Y, M
-
-
 def test_trajectory_set_csr_vs_map_and_reference_semantics(tmp_path, monkeypatch):
     from point_trajectory.optimize.build import particlesfm
     from point_trajectory.trajectory import TrajectoryList
@@ -206,7 +187,7 @@ def test_trajectory_set_csr_vs_map_and_reference_semantics(tmp_path, monkeypatch
     ts.build_invert_indexes()
     for frames, ml in [([3, 4, 5, 6, 7], 3), (list(range(10, 20)), 3), ([0, 1], 1), ([50, 51, 52], 3), ([5, 5, 6], 3)]:
         out = ts.sample_inside_window(frames, min_length=ml)
-        ids, X, Y, M = _reference_sample_inside_window(ref, frames, ml)
+        ids, X, Y, M = reference_sample_inside_window(ref, frames, ml)
         assert out["traj_ids"] == ids
         assert np.array_equal(out["locations"][0], X) and np.array_equal(out["locations"][1], Y)
         assert np.array_equal(out["masks"], M)

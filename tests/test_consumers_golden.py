@@ -8,29 +8,9 @@ GPU part (-m gpu): psfm_traj_to_matches and psfm_window_sample straight from the
 import numpy as np
 import pytest
 
-from _common import golden, regen_inputs
+from _common import check_match_tables, golden, regen_inputs
 
 MATCH_CASES = ["matches_40x56_t12", "matches_24x32_t27_dyn"]
-
-
-def _pairs_in_dict_order(datas, names):
-    """[(src image, tgt image, rows)] in the order the reference's dicts hold them (image order, then first use)."""
-    out = []
-    for i, n in enumerate(names):
-        for key, rows in datas[n].match_pairs.items():
-            a, b = key.split("-")
-            out.append((names.index(a), names.index(b), np.asarray(rows, np.int32).reshape(-1, 2)))
-    return out
-
-
-def _check_against_fixture(datas, names, g):
-    kp = [np.asarray(datas[n].keypoints, np.float64).reshape(-1, 2) for n in names]
-    assert np.array_equal(np.cumsum([0] + [len(k) for k in kp]), g["kp_off"])
-    assert np.array_equal(np.concatenate(kp, 0), g["kp_xy"])
-    pairs = _pairs_in_dict_order(datas, names)
-    assert [p[0] for p in pairs] == g["pair_src"].tolist() and [p[1] for p in pairs] == g["pair_tgt"].tolist()
-    assert np.array_equal(np.cumsum([0] + [len(p[2]) for p in pairs]), g["pair_off"])
-    assert np.array_equal(np.concatenate([p[2] for p in pairs], 0), g["rows"])
 
 
 @pytest.mark.parametrize("name", MATCH_CASES)
@@ -51,7 +31,7 @@ def test_host_match_tables_equal_reference_fixture(name, tmp_path):
     T = int(g["T"])
     names = ["%05d.png" % i for i in range(T)]
     tables = mff.match_tables_host(off, frames, xy, labels, T, remove_dynamic=True)
-    _check_against_fixture(mff.assemble(names, tables, str(tmp_path / "pairs.txt")), names, g)
+    check_match_tables(mff.assemble(names, tables, str(tmp_path / "pairs.txt")), names, g)
 
 
 def test_host_match_tables_reject_frames_outside_the_image_list():
@@ -98,7 +78,7 @@ def test_device_traj_to_matches_equals_reference_fixture(pt, name, tmp_path):
     names = ["%05d.png" % i for i in range(T)]
     for lab in ((torch.from_numpy(labels).cuda(),) if labels.any() else (None, torch.from_numpy(labels).cuda())):
         datas = mff.traj_to_matches_device(ctx, names, str(tmp_path / "pairs.txt"), traj_min_len=3, labels=lab)
-        _check_against_fixture(datas, names, g)
+        check_match_tables(datas, names, g)
     import hashlib
     assert hashlib.sha256(open(str(tmp_path / "pairs.txt")).read().encode()).hexdigest() == str(g["pair_file_hash"])
     # frames beyond the image list are an argument error, not a silent truncation

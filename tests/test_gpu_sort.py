@@ -43,6 +43,20 @@ def test_every_pass_count_and_partial_last_digit(end_bit):
     _check(rng.integers(0, 1 << end_bit, 70_001, dtype=np.uint64).astype(np.uint32), end_bit)
 
 
+@pytest.mark.parametrize("end_bit", [1, 7, 9, 13, 17, 25, 31])
+def test_bits_above_end_bit_are_ignored(end_bit):
+    """include/psfm.h: the keys are sorted by their bits [0, end_bit) -- as rocPRIM's begin_bit / end_bit.  Keys random over all 32
+    bits: the bits above end_bit must not order anything (the last pass of an end_bit that is no multiple of 8 takes a partial
+    digit), and the keys leave whole, in the order of their low bits, values with them."""
+    rng = np.random.default_rng(100 + end_bit)
+    keys = rng.integers(0, 1 << 32, 70_001, dtype=np.uint64).astype(np.uint32)
+    vals = np.arange(keys.size, dtype=np.int32)
+    k, v = _sort(keys, vals, end_bit)
+    order = np.argsort(keys & np.uint32((1 << end_bit) - 1), kind="stable")
+    assert np.array_equal(k, keys[order])
+    assert np.array_equal(v, vals[order])
+
+
 @pytest.mark.parametrize("kind", ["all-equal", "sorted", "reversed", "three-values", "one-digit-varies", "top-digit-only"])
 def test_digit_distributions(kind):
     n = 2 * GROUP + 1234

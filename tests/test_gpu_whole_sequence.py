@@ -1,5 +1,6 @@
 """Whole-sequence parity at BASELINE.json's full sizes, against the CPU oracle on the same tensors: configs[0]'s shape in
-track mode (last test), and the path-consistency path (flow_check x2 + track_optimize + id order) on
+track mode, configs[1]'s (the headline bench.py times) in
+track mode on three flow distributions (last tests), and the path-consistency path (flow_check x2 + track_optimize + id order) on
 
     configs[2] shape   436 x 1024 x   50 frames, sample_ratio 2            (Sintel alley_1 stand-in)
     configs[3] shape  1080 x 1920 x  401 frames, sample_ratio 2            (the 8-GPU config, here on ONE GPU)
@@ -136,3 +137,104 @@ def test_whole_sequence_track_configs0_vs_oracle():
                 assert np.array_equal(R.birth, O.birth) and np.array_equal(R.length, O.length) and np.array_equal(R.xy, O.xy)
     finally:
         ctx.set_chain_mode(0)
+
+
+# BASELINE configs[1] -- the step bench.py times -- on three flow distributions (seeds other than the headline's for hard / realistic)
+CONFIGS1 = [
+    pytest.param(0, dict(EASY), id="configs1-headline"),
+    pytest.param(21, dict(psfm_synth.HARD), id="configs1-hard"),
+    pytest.param(22, dict(psfm_synth.REALISTIC, realistic=True), id="configs1-realistic"),
+]
+
+
+def _assert_track_equal(R, O):
+    assert len(R) == O.n_traj and R.n_points == O.n_points
+    assert np.array_equal(R.birth, O.birth) and np.array_equal(R.length, O.length) and np.array_equal(R.xy, O.xy)
+
+
+@pytest.mark.parametrize("seed,dist", CONFIGS1)
+def test_whole_sequence_track_configs1_vs_oracle(seed, dist):
+    """BASELINE configs[1] (1080 x 1920 x 101 frames, sample_ratio 2, `track`): the headline workload of bench.py, exactly (seed 0,
+    sigma 0.05, 2 occluders), and the same shape on psfm_synth.HARD and psfm_synth.REALISTIC, whose deaths and births load the
+    persistent loop's second phase (births, adoptions) and the finalize's (last, birth) groups hardest.  Against the CPU oracle:
+    the device's occlusion maps on all 100 pairs bit-equal; ids / lengths / positions bit-equal for psfm_connect in mode 0 (flow_check
+    fused into the persistent loop: the form the bench times -- the policy must pick it, chain_mode 2) and mode 1 (per-frame launches),
+    and for flow_check + psfm_track in modes 2 and 1; the saved set (device-side length >= 3 filter) equal to the oracle's.
+    What the three cover (the oracle's figures on the MI355X box; PSFM_WHOLE_SEQ_REPORT collects them):
+
+                    trajectories   points        born after frame 0   shorter than 3   mode 0 ran
+        headline    2 073 277      51 636 047    1 554 877              192 396        persistent loop (chain_mode 2)
+        hard        4 293 168      39 994 681    3 774 768              768 664        persistent loop (chain_mode 2)
+        realistic   4 869 295      44 029 024    4 350 895              952 424        persistent loop (chain_mode 2)
+
+    hard / realistic: ~2.5x the headline's births and 4-5x its short tracks -- and neither leaves the persistent loop (no lane-table
+    retry, no hand-over to per-frame launches), so the fused loop is asserted for all three."""
+    import psutil
+    import torch
+    from oracle import oracle as orc
+    from point_trajectory import _hip
+    from point_trajectory.trajectory import run_connect, run_track, result_to_trajectory_set, _result_to_host
+    from point_trajectory.utils import flow_check_device
+    T, H, W, r, thres = 101, 1080, 1920, 2, 1.0
+    need = 2 * (T - 1) * H * W * 8 + (T - 1) * H * W + 2 * 16 * ((H + r - 1) // r) * ((W + r - 1) // r) * T
+    if psutil.virtual_memory().available < 1.3 * need:
+        pytest.skip("host memory: %.1f GB needed for the oracle's copy of the sequence" % (need / 1e9))
+    orc.set_num_threads(min(16, os.cpu_count() or 1))
+    if dist.get("realistic"):
+        d = psfm_synth.synth_realistic_torch(T, H, W, seed=seed, stride2=False, device="cuda", **{k: v for k, v in dist.items() if k != "realistic"})
+    else:
+        d = psfm_synth.synth_sequence_torch(T, H, W, seed=seed, stride2=False, device="cuda", **dist)
+    ff_d, fb_d = d["flows_f"], d["flows_b"]
+    del d
+    # the oracle on host copies of the same tensors
+    ff = ff_d.cpu().numpy()
+    fb = fb_d.cpu().numpy()
+    _, occ_o = orc.flow_check(list(ff), list(fb), thres)
+    del fb
+    O = orc.track(list(ff), occ_o, r)
+    del ff
+    born_late, short = int((O.birth > 0).sum()), int((O.length < 3).sum())
+    _, occ = flow_check_device(ff_d, fb_d, thres)
+    for k in range(T - 1):
+        assert np.array_equal(occ[k].cpu().numpy().astype(bool), occ_o[k]), k
+    del occ_o
+    ctx = _hip.context()
+    modes = {}
+    try:
+        ctx.set_chain_mode(0)
+        info = run_connect(ff_d, fb_d, None, None, thres, r, return_device=True)
+        modes["connect-0"] = int(info.chain_mode)
+        R = _result_to_host(ctx, info)
+        _assert_track_equal(R, O)
+        del R
+        ts = result_to_trajectory_set(ctx, info, 3)
+        ids, birth, length, off, xy = ts._csr[:5]
+        keep = np.flatnonzero(O.length >= 3)
+        assert np.array_equal(ids, keep) and np.array_equal(birth, O.birth[keep]) and np.array_equal(length, O.length[keep])
+        assert off[0] == 0 and np.array_equal(np.diff(off), O.length[keep].astype(np.int64))
+        assert np.array_equal(xy, O.xy[np.repeat(O.length >= 3, O.length)])
+        del ts, ids, birth, length, off, xy
+        for mode, form in ((1, "connect"), (2, "track"), (1, "track")):
+            ctx.set_chain_mode(mode)
+            if form == "connect":
+                R = run_connect(ff_d, fb_d, None, None, thres, r)
+            else:
+                R = run_track(ff_d, occ, None, None, r)
+            modes["%s-%d" % (form, mode)] = int(R.info["chain_mode"])
+            _assert_track_equal(R, O)
+            del R
+    finally:
+        ctx.set_chain_mode(0)
+    out = os.environ.get("PSFM_WHOLE_SEQ_REPORT")
+    if out:
+        import json
+        with open(out, "a") as fh:
+            fh.write(json.dumps({"shape": [H, W, T, r], "seed": seed, "trajectories": int(O.n_traj), "points": int(O.n_points),
+                                 "born_after_frame0": born_late, "shorter_than_3": short, "chain_modes": modes,
+                                 "distribution": dist}) + "\n")
+    # what each distribution is there for: births after frame 0 and tracks the saved set drops; far more of both off the headline
+    assert born_late > 1_000_000 and short > 100_000, (born_late, short)
+    if seed != 0:
+        assert born_late > 3_000_000 and short > 500_000, (born_late, short)
+    # the fused persistent loop ran the mode-0 call: the path bench.py times
+    assert modes == {"connect-0": 2, "connect-1": 1, "track-2": 2, "track-1": 1}, modes
