@@ -18,6 +18,7 @@
  *   psfm_connect_batch      the same for a batch of sequences: the loop of run_particlesfm.py:168-176
  *   psfm_result_*           the list of Trajectory objects those functions return and the
  *                           id / min-length rule of main_connect_point_trajectories.py:56-60
+ *   psfm_labels_*           motion_seg/main_motion_segmentation.py:89-129 (per-window predictions -> labelled track.npy)
  *
  * Conventions
  *   - plain C, no C++/torch types.  Every data pointer is a DEVICE pointer
@@ -285,6 +286,51 @@ psfm_status psfm_traj_to_matches(psfm_ctx* ctx, int n_img, int sample_k, const u
                                  int64_t* n_matches_host, int64_t* n_pairs_host, void* stream);
 psfm_status psfm_matches_copy(psfm_ctx* ctx, int64_t* kp_off_host, double* kp_xy_host, int64_t* pair_key_host,
                               int64_t* pair_off_host, int64_t* pair_first_host, int32_t* rows_host, void* stream);
+
+/* motion_seg/main_motion_segmentation.py:89-129: the network's per-window, per-trajectory predictions merged into the labelled
+ * trajectory set that sfm/matches_from_flow.py consumes -- the dict loop of :92-112 and the saved dict of :122-129 -- over the saved
+ * set that psfm_result_filter left in HBM, without a track.npy round trip.  What the reference's loop produces, and this reproduces:
+ *   - a trajectory enters with the first row that names it and has a point inside that row's window (:100-103); the set lists the
+ *     trajectories in that order of first appearance (window, then row), NOT by ascending id;
+ *   - a point carries the prediction of the FIRST window that covered it; a later window only adds the frames the trajectory does
+ *     not hold yet (:105-112), so a trajectory can carry both labels;
+ *   - only points inside windows where the trajectory was sampled enter: a trajectory that psfm_window_sample left out of a middle
+ *     window (max_num_tracks) has a GAP in its frames, one with fewer than min_length observations in every window never enters.
+ *     The labelled set therefore carries explicit per-point frames and is not the saved set with a label array on top.
+ * psfm_labels_begin         needs a non-empty saved set in the context (else PSFM_ERR_ARG); clears the merge state and ties it to
+ *                           that saved set: a later psfm_result_filter / psfm_track / psfm_connect / psfm_connect_batch on the
+ *                           context voids it, and psfm_labels_merge_window / psfm_labels_finish then return PSFM_ERR_ARG.
+ * psfm_labels_merge_window  one window, in stream order: row i says trajectory ids_dev[i] (i32, an id of the saved set) is dynamic
+ *                           (pred_dev[i] != 0) or static on frames [frame0, frame0 + n_frames).  ASYNCHRONOUS: one launch, no host
+ *                           synchronisation, no allocation -- it can be enqueued right behind the network's output tensor.  k = 0 is
+ *                           a no-op.  Preconditions: ids are unique within a call (psfm_window_sample guarantees it; the result for
+ *                           duplicates is unspecified, every access stays in bounds); fewer than 2^32 - 1 rows over all windows.  A
+ *                           row whose trajectory has no point in the window is ignored (the reference would file an empty entry,
+ *                           which changes no match; psfm_window_sample never emits such a row).  An id that is not in the saved
+ *                           set raises a device-side flag: the call stays asynchronous, psfm_labels_finish reports PSFM_ERR_ARG.
+ * psfm_labels_finish        builds the labelled set in the context and returns its sizes; synchronises `stream`.  CSR in order of
+ *                           first appearance, a trajectory's points in time order:
+ *                             ids (n_traj) i32, off (n_traj+1) i64, frame_ids (n_points) i32, xy (n_points,2) f64,
+ *                             labels (n_points) u8 (1 = dynamic)
+ *                           No window merged: the empty set (n_traj = 0).  More windows may be merged and finish called again.
+ * psfm_labels_device        the DEVICE pointers of that CSR (any argument may be NULL); psfm_labels_copy copies it into caller-provided
+ *                           buffers, HOST or DEVICE (the direction follows from the pointer), any may be NULL, and synchronises
+ *                           `stream`.  The labelled set is a copy of its own: it stays valid when the saved set changes.
+ * psfm_labels_to_matches    sfm/matches_from_flow.py:51-118 over the labelled set: the tables of psfm_traj_to_matches (same
+ *                           pipeline, same context tables -- read them with psfm_matches_copy), with the trajectories in the
+ *                           set's order (the dict order :67 iterates in), a point's frame from frame_ids, and the kept points =
+ *                           labels == 0 when remove_dynamic != 0 (:71-74), all points otherwise.  A frame outside [0, n_img) is
+ *                           PSFM_ERR_ARG.  Synchronises `stream`. */
+psfm_status psfm_labels_begin(psfm_ctx* ctx, void* stream);
+psfm_status psfm_labels_merge_window(psfm_ctx* ctx, int frame0, int n_frames, const int32_t* ids_dev, const uint8_t* pred_dev,
+                                     int64_t k, void* stream);
+psfm_status psfm_labels_finish(psfm_ctx* ctx, int64_t* n_traj_host, int64_t* n_points_host, void* stream);
+psfm_status psfm_labels_device(psfm_ctx* ctx, const int32_t** ids, const int64_t** off, const int32_t** frame_ids, const double** xy,
+                               const uint8_t** labels);
+psfm_status psfm_labels_copy(psfm_ctx* ctx, int32_t* ids_out, int64_t* off_out, int32_t* frame_ids_out, double* xy_out,
+                             uint8_t* labels_out, void* stream);
+psfm_status psfm_labels_to_matches(psfm_ctx* ctx, int n_img, int sample_k, int remove_dynamic, int64_t* n_kp_host,
+                                   int64_t* n_matches_host, int64_t* n_pairs_host, void* stream);
 
 /* ONE sequence over several processes / GPUs, exactly (psfm_dist.connect_sharded drives these).
  * The tracks are split by the row band of the stride-r grid they are born on: this process owns the births on grid points

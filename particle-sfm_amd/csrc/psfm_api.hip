@@ -177,7 +177,8 @@ extern "C" psfm_status psfm_ctx_destroy(psfm_ctx* c)
                        &c->scan_tmp, &c->fin_marks, &c->res_birth, &c->res_len, &c->res_off, &c->res_xy, &c->sol_x, &c->sol_state,
                        &c->sol_partials, &c->sol_ctrl, &c->sol_misc, &c->sol_stats, &c->sol_fused, &c->sol_bar, &c->sol_list, &c->occ_own, &c->occ2_own,
                        &c->handoff, &c->seg_info, &c->seg_table, &c->persist_bar, &c->batch_tab, &c->batch_ws, &c->batch_fc, &c->win_ws, &c->flt_ids, &c->flt_birth, &c->flt_len, &c->flt_off, &c->flt_xy,
-                       &c->mt_kp_off, &c->mt_q, &c->mt_pts, &c->mt_kp_ind, &c->mt_kp_xy, &c->mt_moff, &c->mt_keys, &c->mt_rows, &c->mt_gid, &c->mt_pairs};
+                       &c->mt_kp_off, &c->mt_q, &c->mt_pts, &c->mt_kp_ind, &c->mt_kp_xy, &c->mt_moff, &c->mt_keys, &c->mt_rows, &c->mt_gid, &c->mt_pairs,
+                       &c->lb_state, &c->lb_first, &c->lb_flag, &c->lb_ws, &c->lb_ids, &c->lb_off, &c->lb_frames, &c->lb_xy, &c->lb_labels};
     for (auto b : bufs) b->release();
     for (void*& q : c->peer_opened) { if (q) (void)hipIpcCloseMemHandle(q); q = nullptr; }
     c->peer_area.release();
@@ -778,6 +779,7 @@ extern "C" psfm_status psfm_track(psfm_ctx* c, const float* flows, const uint8_t
                                   void* stream)
 {
     PSFM_CHECK_CTX(c);   // (selects the context's device: the residency query below is per device)
+    c->res_gen++;        // (labels merged over the saved set of the result this call replaces are void: psfm_labels_begin)
     PsfmGate gate(c->device, psfm_wants_persist(c, flows_f2 != nullptr, h, w, ratio, false));
     return psfm_track_impl(c, flows, occ, flows_f2, occ_s2, n_flows, h, w, ratio, info, stream, nullptr, gate);
 }
@@ -791,6 +793,7 @@ extern "C" psfm_status psfm_connect(psfm_ctx* c, const float* flows_f, const flo
                                     uint8_t* occ, uint8_t* occ_s2, psfm_track_info* info, void* stream)
 {
     PSFM_CHECK_CTX(c);
+    c->res_gen++;
     const bool optimize = flows_f2 != nullptr;
     PsfmGate gate(c->device, psfm_wants_persist(c, optimize, h, w, ratio, true));
     if (n_flows < 1 || !psfm_frame_ok(h, w) || !flows_f || !flows_b || (optimize && n_flows > 1 && !flows_b2)) {

@@ -74,6 +74,7 @@ extern "C" psfm_status psfm_connect_batch(psfm_ctx* const* ctxs, int n_seq, cons
         return PSFM_ERR_ARG;
     }
     const bool optimize = flows_f2 != nullptr;
+    for (int i = 0; i < n_seq; ++i) if (ctxs[i]) ctxs[i]->res_gen++;
     for (int i = 0; i < n_seq; ++i) {
         if (!ctxs[i] || ctxs[i]->device != ctxs[0]->device) { psfm_set_error("psfm_connect_batch: context %d is NULL or on another device", i); return PSFM_ERR_ARG; }
         for (int j = 0; j < i; ++j) if (ctxs[j] == ctxs[i]) { psfm_set_error("psfm_connect_batch: context %d given twice (one per sequence)", i); return PSFM_ERR_ARG; }

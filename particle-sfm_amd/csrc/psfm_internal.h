@@ -204,6 +204,16 @@ struct psfm_ctx {
     PsfmBuf mt_kp_off, mt_q, mt_pts, mt_kp_ind, mt_kp_xy, mt_moff, mt_keys, mt_rows, mt_gid, mt_pairs;
     int64_t mt_n_kp = 0, mt_n_m = 0, mt_n_pairs = 0;
     int mt_n_img = 0;
+    // psfm_labels_* (psfm_labels.hip): per-window motion labels merged over the saved set, and the labelled set built from them
+    uint64_t res_gen = 0;                // bumped by every entry point that replaces the result or the saved set (psfm_track, psfm_connect,
+                                         // psfm_connect_batch, psfm_result_filter): what psfm_labels_begin ties its state to
+    uint64_t lb_gen = 0;
+    bool lb_active = false, lb_finished = false;
+    int64_t lb_rows = 0;                 // rows merged so far (the sequence number of the next window's row 0)
+    PsfmBuf lb_state, lb_first, lb_flag; // per saved point u8 (255 unlabelled, 0 static, 1 dynamic); per saved trajectory u32; error flag
+    PsfmBuf lb_ws;                       // finish: counts, sort halves
+    PsfmBuf lb_ids, lb_off, lb_frames, lb_xy, lb_labels;   // the labelled set, CSR in order of first appearance
+    int64_t lb_n_traj = 0, lb_n_points = 0;
     hipStream_t side_stream = nullptr;   // flow_check of psfm_connect runs here, ahead of the frame loop
     hipStream_t copy_stream = nullptr;   // psfm_load_flo_stack: H2D copies out of the pinned ring
     hipStream_t copy_stream2 = nullptr;  // ... every second slot's copies (two SDMA engines; PSFM_FLO_COPY_STREAMS=1: one)
@@ -269,6 +279,18 @@ psfm_status psfm_launch_batch_pack(const void* tab_dev, const int* lo, int n_seq
 // one segmented finalize for all sequences of a batch (psfm_finalize.hip): ONE host synchronisation, ONE sort.  dims[i] are the
 // sequences' dimensions (same key format); the shared workspace is `own`'s, results land in every context's own res_* buffers
 psfm_status psfm_finalize_batch(psfm_ctx* own, psfm_ctx* const* ctxs, const PsfmTrackDims* dims, int n_seq, hipStream_t s);
+
+// ---- match tables (psfm_matches.hip): the pipeline of psfm_traj_to_matches over any CSR of trajectories in HBM ----------------
+// A point's frame is birth[t] + (p - off[t]) when `frames` is NULL (the saved set: contiguous frames), frames[p] otherwise (the
+// labelled set: explicit frames, gaps allowed).  labels: NULL = keep every point, else points with labels[p] != 0 are dropped.
+struct PsfmMatchSrc {
+    int64_t k = 0, n_pts = 0;
+    const int64_t* off = nullptr; const int* birth = nullptr; const int* frames = nullptr;
+    const double2* xy = nullptr; const uint8_t* labels = nullptr;
+    const char* who = "psfm_traj_to_matches";
+};
+psfm_status psfm_match_tables(psfm_ctx* c, const PsfmMatchSrc& src, int n_img, int sample_k, int64_t* n_kp_host, int64_t* n_matches_host,
+                              int64_t* n_pairs_host, hipStream_t s);
 
 // ---- persistent frame loop (psfm_persist.hip) ---------------------------------------------------
 int psfm_persist_max_blocks(psfm_ctx* c);

@@ -44,7 +44,8 @@ __global__ __launch_bounds__(PM_BLOCK) void pm_keep_kernel(const uint8_t* __rest
 // kept point q (compacted index): its frame, its flat point, its trajectory
 __global__ __launch_bounds__(PM_BLOCK) void pm_compact_kernel(const uint8_t* __restrict__ labels, const int64_t* __restrict__ q_of,
                                                              int64_t n_pts, const int64_t* __restrict__ off, int64_t k,
-                                                             const int* __restrict__ birth, unsigned* __restrict__ kfr,
+                                                             const int* __restrict__ birth, const int* __restrict__ frames,
+                                                             unsigned* __restrict__ kfr,
                                                              int64_t* __restrict__ kpt, int* __restrict__ ktraj,
                                                              unsigned* __restrict__ iota, int* __restrict__ bad, int n_img)
 {
@@ -52,7 +53,7 @@ __global__ __launch_bounds__(PM_BLOCK) void pm_compact_kernel(const uint8_t* __r
     if (p >= n_pts || (labels && labels[p] != 0)) return;
     const int64_t q = q_of[p];
     const int t = pm_owner(off, k, p);
-    const int f = birth[t] + (int)(p - off[t]);
+    const int f = frames ? frames[p] : birth[t] + (int)(p - off[t]);    // explicit frames (the labelled set) or birth + offset
     // a frame outside the image list is an argument error, reported by the host once this pass is over; the entry is still
     // written (frame 0) -- the sort and the kernels behind it run before the host looks at the flag and must stay in bounds
     const bool outside = f < 0 || f >= n_img;
@@ -181,25 +182,27 @@ static int pm_bits(unsigned long long v)   // bits needed for values < v
 
 static unsigned pm_grid(int64_t n) { return (unsigned)((n + PM_BLOCK - 1) / PM_BLOCK); }
 
-extern "C" psfm_status psfm_traj_to_matches(psfm_ctx* c, int n_img, int sample_k, const uint8_t* labels, int64_t* n_kp_host,
-                                            int64_t* n_matches_host, int64_t* n_pairs_host, void* stream)
+// The pipeline of the file header over the trajectories `src` describes; both entries (psfm_traj_to_matches over the saved set,
+// psfm_labels_to_matches over the labelled set) run it and differ only in where a point's frame and label come from.
+psfm_status psfm_match_tables(psfm_ctx* c, const PsfmMatchSrc& src, int n_img, int sample_k, int64_t* n_kp_host, int64_t* n_matches_host,
+                              int64_t* n_pairs_host, hipStream_t s)
 {
     if (!c || !n_kp_host || !n_matches_host || !n_pairs_host || n_img < 1 || sample_k < 1) {
-        psfm_set_error("psfm_traj_to_matches: bad argument (n_img=%d sample_k=%d)", n_img, sample_k);
+        psfm_set_error("%s: bad argument (n_img=%d sample_k=%d)", src.who, n_img, sample_k);
         return PSFM_ERR_ARG;
     }
+    const uint8_t* labels = src.labels;
     PSFM_HIP(hipSetDevice(c->device));
     PsfmGate gate(c->device, 0);
-    hipStream_t s = (hipStream_t)stream;
     *n_kp_host = *n_matches_host = *n_pairs_host = 0;
     c->mt_n_kp = c->mt_n_m = c->mt_n_pairs = 0; c->mt_n_img = n_img;
     psfm_status st;
     if ((st = c->mt_kp_off.ensure(8 * (size_t)(n_img + 1))) != PSFM_OK) return st;
     PSFM_HIP(hipMemsetAsync(c->mt_kp_off.p, 0, 8 * (size_t)(n_img + 1), s));
-    const int64_t k = c->flt_n_traj, n_pts = c->flt_n_points;
+    const int64_t k = src.k, n_pts = src.n_pts;
     if (k == 0 || n_pts == 0) { PSFM_HIP(hipStreamSynchronize(s)); return PSFM_OK; }
-    if (n_pts >= 0xffffffffll) { psfm_set_error("psfm_traj_to_matches: more than 2^32 points"); return PSFM_ERR_ARG; }
-    const int64_t* off = c->flt_off.as<int64_t>();
+    if (n_pts >= 0xffffffffll) { psfm_set_error("%s: more than 2^32 points", src.who); return PSFM_ERR_ARG; }
+    const int64_t* off = src.off;
     int64_t* h = (int64_t*)((char*)c->host_pinned + 272);    // [0] scalar read-back, [1] bad-frame flag
     // ---- keep + compaction ----
     if ((st = c->mt_q.ensure(8 * (size_t)(n_pts + 1))) != PSFM_OK) return st;
@@ -224,7 +227,7 @@ extern "C" psfm_status psfm_traj_to_matches(psfm_ctx* c, int n_img, int sample_k
     if ((st = c->mt_kp_xy.ensure(16 * (size_t)n_kept)) != PSFM_OK) return st;
     PSFM_HIP(hipMemsetAsync(bad, 0, 4, s));
     hipLaunchKernelGGL(pm_compact_kernel, dim3(pm_grid(n_pts)), dim3(PM_BLOCK), 0, s, labels, (const int64_t*)q_of, n_pts, off, k,
-                       c->flt_birth.as<int>(), kfr, kpt, ktraj, iota, bad, n_img);
+                       src.birth, src.frames, kfr, kpt, ktraj, iota, bad, n_img);
     {
         size_t bytes = 0;
         const int bits = pm_bits((unsigned long long)n_img);
@@ -235,7 +238,7 @@ extern "C" psfm_status psfm_traj_to_matches(psfm_ctx* c, int n_img, int sample_k
     hipLaunchKernelGGL(pm_kp_off_kernel, dim3(pm_grid(n_img + 1)), dim3(PM_BLOCK), 0, s, (const unsigned*)fsorted, n_kept, n_img,
                        c->mt_kp_off.as<int64_t>());
     hipLaunchKernelGGL(pm_kp_kernel, dim3(pm_grid(n_kept)), dim3(PM_BLOCK), 0, s, (const unsigned*)fsorted, (const unsigned*)order, n_kept,
-                       (const int64_t*)c->mt_kp_off.as<int64_t>(), (const int64_t*)kpt, c->flt_xy.as<double2>(), c->mt_kp_ind.as<int>(),
+                       (const int64_t*)c->mt_kp_off.as<int64_t>(), (const int64_t*)kpt, src.xy, c->mt_kp_ind.as<int>(),
                        c->mt_kp_xy.as<double2>());
     // ---- matches: count, scan, emit in loop order ----
     if ((st = c->mt_moff.ensure(8 * (size_t)(n_kept + 1))) != PSFM_OK) return st;
@@ -246,7 +249,7 @@ extern "C" psfm_status psfm_traj_to_matches(psfm_ctx* c, int n_img, int sample_k
     PSFM_HIP(hipMemcpyAsync(h, c->mt_moff.as<int64_t>() + n_kept, 8, hipMemcpyDeviceToHost, s));
     PSFM_HIP(hipMemcpyAsync(h + 1, bad, 4, hipMemcpyDeviceToHost, s));
     PSFM_HIP(hipStreamSynchronize(s));
-    if ((int)(h[1] & 0xffffffff) != 0) { psfm_set_error("psfm_traj_to_matches: a trajectory has a frame outside [0, n_img=%d)", n_img); return PSFM_ERR_ARG; }
+    if ((int)(h[1] & 0xffffffff) != 0) { psfm_set_error("%s: a trajectory has a frame outside [0, n_img=%d)", src.who, n_img); return PSFM_ERR_ARG; }
     const int64_t n_m = h[0];
     c->mt_n_m = n_m;
     *n_matches_host = n_m;
@@ -286,6 +289,16 @@ extern "C" psfm_status psfm_traj_to_matches(psfm_ctx* c, int n_img, int sample_k
     PSFM_HIP(hipGetLastError());
     PSFM_HIP(hipStreamSynchronize(s));
     return PSFM_OK;
+}
+
+extern "C" psfm_status psfm_traj_to_matches(psfm_ctx* c, int n_img, int sample_k, const uint8_t* labels, int64_t* n_kp_host,
+                                            int64_t* n_matches_host, int64_t* n_pairs_host, void* stream)
+{
+    if (!c) { psfm_set_error("psfm_traj_to_matches: bad argument (n_img=%d sample_k=%d)", n_img, sample_k); return PSFM_ERR_ARG; }
+    PsfmMatchSrc src;
+    src.k = c->flt_n_traj; src.n_pts = c->flt_n_points;
+    src.off = c->flt_off.as<int64_t>(); src.birth = c->flt_birth.as<int>(); src.xy = c->flt_xy.as<double2>(); src.labels = labels;
+    return psfm_match_tables(c, src, n_img, sample_k, n_kp_host, n_matches_host, n_pairs_host, (hipStream_t)stream);
 }
 
 extern "C" psfm_status psfm_matches_copy(psfm_ctx* c, int64_t* kp_off_host, double* kp_xy_host, int64_t* pair_key_host,

@@ -206,6 +206,7 @@ extern "C" psfm_status psfm_result_filter(psfm_ctx* c, int traj_min_len, int64_t
     const int64_t n = c->res_n_traj;
     *n_traj_host = 0; *n_points_host = 0;
     c->flt_n_traj = c->flt_n_points = 0;
+    c->res_gen++;        // (a new saved set: labels merged over the previous one are void, psfm_labels_begin)
     if (n == 0) return PSFM_OK;
     psfm_status st;
     const size_t o_iota = ((size_t)n + 255) / 256 * 256, o_cnt = o_iota + 4 * (size_t)n, total = o_cnt + 256;

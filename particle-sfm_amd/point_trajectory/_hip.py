@@ -25,6 +25,7 @@ EXPORTS = [
     "psfm_shard_solve_control_chain_async", "psfm_shard_solve_poll", "psfm_shard_solve_local", "psfm_shard_solve_redo_local", "psfm_connect_batch", "psfm_solver_launches", "psfm_ctx_set_resident_budget", "psfm_resident_capacity", "psfm_load_flo_stack",
     "psfm_path_consistency_eval", "psfm_sort_records",
     "psfm_shard_peer_area", "psfm_shard_peer_epoch", "psfm_shard_peer_open", "psfm_shard_peer_connect", "psfm_shard_solve_blocks", "psfm_shard_solve_peer",
+    "psfm_labels_begin", "psfm_labels_merge_window", "psfm_labels_finish", "psfm_labels_device", "psfm_labels_copy", "psfm_labels_to_matches",
 ]
 
 
@@ -102,6 +103,12 @@ def lib():
                                      ctypes.POINTER(i64), vp]
     L.psfm_traj_to_matches.argtypes = [vp, i32, i32, vp, ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(i64), vp]
     L.psfm_matches_copy.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
+    L.psfm_labels_begin.argtypes = [vp, vp]
+    L.psfm_labels_merge_window.argtypes = [vp, i32, i32, vp, vp, i64, vp]
+    L.psfm_labels_finish.argtypes = [vp, ctypes.POINTER(i64), ctypes.POINTER(i64), vp]
+    L.psfm_labels_device.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp)]
+    L.psfm_labels_copy.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.psfm_labels_to_matches.argtypes = [vp, i32, i32, i32, ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(i64), vp]
     L.psfm_shard_begin.argtypes = [vp, i32, i32, i32, i32, i64, i64, i32, vp, i64, vp]
     L.psfm_shard_step.argtypes = [vp, vp, vp, i32, vp]
     L.psfm_shard_solve_export.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp]

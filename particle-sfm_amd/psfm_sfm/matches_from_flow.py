@@ -138,20 +138,12 @@ def traj_to_matches(img_dir, traj_dir, match_list_file, remove_dynamic=True, sam
     return assemble(image_names, tables, match_list_file, as_arrays)
 
 
-def match_tables_device(ctx, n_img, traj_min_len=3, sample_k=SAMPLE_K, labels=None):
-    """The same tables from the result the last psfm_track / psfm_connect of `ctx` left in HBM: the saved set
-    (length >= traj_min_len, psfm_result_filter) -> psfm_traj_to_matches -> one copy of the finished tables.
-    labels: optional (n_points,) uint8 device tensor over the saved set's points (1 = dynamic, dropped)."""
+def _copy_tables(ctx, n_img, n_kp, n_m, n_p):
+    """psfm_matches_copy: the finished tables of the context, one copy."""
     import ctypes
     from point_trajectory import _hip
     L = _hip.lib()
     sp = _hip.current_stream_ptr(ctx.device)
-    k, npt = ctypes.c_int64(0), ctypes.c_int64(0)
-    _hip.check(L.psfm_result_filter(ctx.handle, int(traj_min_len), ctypes.byref(k), ctypes.byref(npt), sp))
-    n_kp, n_m, n_p = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
-    _hip.check(L.psfm_traj_to_matches(ctx.handle, int(n_img), int(sample_k), _hip.ptr(labels), ctypes.byref(n_kp),
-                                      ctypes.byref(n_m), ctypes.byref(n_p), sp))
-    n_kp, n_m, n_p = int(n_kp.value), int(n_m.value), int(n_p.value)
     kp_off = np.zeros(n_img + 1, np.int64)
     kp_xy = np.empty((n_kp, 2), np.float64)
     pair_key = np.empty(n_p, np.int64)
@@ -163,8 +155,46 @@ def match_tables_device(ctx, n_img, traj_min_len=3, sample_k=SAMPLE_K, labels=No
     return kp_off, kp_xy, pair_key, pair_off, pair_first, rows
 
 
+def match_tables_device(ctx, n_img, traj_min_len=3, sample_k=SAMPLE_K, labels=None):
+    """The same tables from the result the last psfm_track / psfm_connect of `ctx` left in HBM: the saved set
+    (length >= traj_min_len, psfm_result_filter) -> psfm_traj_to_matches -> one copy of the finished tables.
+    labels: optional (n_points,) uint8 device tensor over the saved set's points (1 = dynamic, dropped).  This equals the
+    reference only when EVERY saved point is labelled (--assume_static, or labels from elsewhere); the set motion segmentation
+    produces drops and reorders trajectories -- use match_tables_labelled_device for it."""
+    import ctypes
+    from point_trajectory import _hip
+    L = _hip.lib()
+    sp = _hip.current_stream_ptr(ctx.device)
+    k, npt = ctypes.c_int64(0), ctypes.c_int64(0)
+    _hip.check(L.psfm_result_filter(ctx.handle, int(traj_min_len), ctypes.byref(k), ctypes.byref(npt), sp))
+    n_kp, n_m, n_p = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+    _hip.check(L.psfm_traj_to_matches(ctx.handle, int(n_img), int(sample_k), _hip.ptr(labels), ctypes.byref(n_kp),
+                                      ctypes.byref(n_m), ctypes.byref(n_p), sp))
+    return _copy_tables(ctx, n_img, int(n_kp.value), int(n_m.value), int(n_p.value))
+
+
+def match_tables_labelled_device(ctx, n_img, remove_dynamic=True, sample_k=SAMPLE_K):
+    """The tables over the labelled set that psfm_labels_finish (psfm_motion_seg.merge_labels.LabelMerger.finish) left in `ctx`:
+    trajectories in the set's order of first appearance -- the dict order the reference iterates in (:67) --, frames from the set's
+    frame_ids (gaps allowed), kept points = labels == 0 when remove_dynamic (:71-74), all points otherwise."""
+    import ctypes
+    from point_trajectory import _hip
+    L = _hip.lib()
+    n_kp, n_m, n_p = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+    _hip.check(L.psfm_labels_to_matches(ctx.handle, int(n_img), int(sample_k), 1 if remove_dynamic else 0, ctypes.byref(n_kp),
+                                        ctypes.byref(n_m), ctypes.byref(n_p), _hip.current_stream_ptr(ctx.device)))
+    return _copy_tables(ctx, n_img, int(n_kp.value), int(n_m.value), int(n_p.value))
+
+
 def traj_to_matches_device(ctx, image_names, match_list_file, traj_min_len=3, sample_k=SAMPLE_K, labels=None, as_arrays=True):
     """traj_to_matches without the track.npy round trip (e.g. --assume_static, where the trajectory stage feeds SfM
     directly, run_particlesfm.py:114): tables from HBM, assembled like the host path."""
     tables = match_tables_device(ctx, len(image_names), traj_min_len, sample_k, labels)
+    return assemble(list(image_names), tables, match_list_file, as_arrays)
+
+
+def traj_to_matches_labelled_device(ctx, image_names, match_list_file, remove_dynamic=True, sample_k=SAMPLE_K, as_arrays=True):
+    """traj_to_matches over the labelled set in HBM (connect -> window tensors -> network -> LabelMerger -> here: no labelled
+    track.npy round trip), assembled like the host path."""
+    tables = match_tables_labelled_device(ctx, len(image_names), remove_dynamic, sample_k)
     return assemble(list(image_names), tables, match_list_file, as_arrays)
