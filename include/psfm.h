@@ -18,6 +18,7 @@
  *   psfm_connect_batch      the same for a batch of sequences: the loop of run_particlesfm.py:168-176
  *   psfm_result_*           the list of Trajectory objects those functions return and the
  *                           id / min-length rule of main_connect_point_trajectories.py:56-60
+ *   psfm_traj_augment       motion_seg/core/network/traj_oa_depth.py:72-114 augment_traj() (the classifier's 10-channel input)
  *   psfm_labels_*           motion_seg/main_motion_segmentation.py:89-129 (per-window predictions -> labelled track.npy)
  *
  * Conventions
@@ -268,6 +269,26 @@ psfm_status psfm_window_sample(psfm_ctx* ctx, int frame0, int n_frames, int traj
                                int64_t max_num_tracks, uint64_t seed, int raw_h, int raw_w, int in_h, int in_w,
                                int64_t capacity, int32_t* ids_out, double* xy_raw, double* xy_norm, double* mask_absent,
                                int64_t* k_host, void* stream);
+
+/* The motion classifier's input step -- traj_oa_depth.augment_traj with image_grid, depth_project and gather_point
+ * (motion_seg/core/network/traj_oa_depth.py:72-114) behind the host glue of motion_seg/main_motion_segmentation.py:71-78 -- from
+ * exactly what psfm_window_sample wrote: xy_norm (k,n_frames,2) f64, mask_absent (k,n_frames) f64, plus the depth maps at the
+ * network input size, depth (n_frames,h,w) f32.  out is the reference's [1,10,k,n_frames] fp32 tensor, contiguous; planes:
+ *   0-1 the coordinates cast to f32 (.float())   2-3 their frame-to-frame motion   4-6 the back-projected point
+ *   depth * (Kinv @ (px,py,1)) of the pixel under the trajectory   7-9 its motion.
+ * Bit-equal to the reference: every operation is an individually rounded fp32 operation in the reference's order (no FMA), and
+ * the point cloud of every pixel ([B,3,H,W,L] in the reference) is never materialised.  Kept quirks of gather_point (:97-98):
+ *   - pixel index = (int)(y*h) * w + (int)(x*w), truncating, clamped to [0, h*w-1]: x == 1.0 gives column w, the first pixel of
+ *     the NEXT row; y == 1.0 leaves the image and is clamped to the last pixel;
+ *   - a padded slot has coordinates 0, gathers pixel 0 of its frame and carries that 3-D point, not zero;
+ *   - motion at frame l < n_frames-1 is (v[l+1] - v[l]) * (1 - mask_absent[l+1]) (:109-112): only the LATER frame's mask gates
+ *     it, so a padded slot followed by a present one has non-zero motion; the last frame's motion is 0.
+ * Non-finite coordinates (finite flows produce none) give unspecified values; every access stays in bounds.
+ * kinv_host: 9 floats on the HOST, row-major K^-1 (image_grid: fx = fy = (h+w)/2, cx = w/2, cy = h/2, inverted in f64, cast to
+ * f32).  ASYNCHRONOUS: one launch on `stream`, no allocation, no host synchronisation.  k = 0 is a no-op.  PSFM_ERR_ARG: a NULL
+ * pointer with k > 0, k < 0, n_frames < 1, h or w < 1, h*w or 10*k*n_frames above 2^31 - 1 (the kernel's 32-bit indices). */
+psfm_status psfm_traj_augment(psfm_ctx* ctx, const double* xy_norm, const double* mask_absent, const float* depth, int64_t k,
+                              int n_frames, int h, int w, const float* kinv_host, float* out, void* stream);
 
 /* sfm/matches_from_flow.py:51-118 (traj_to_matches) from the saved set that psfm_result_filter left in HBM -- the
  * reference's per-trajectory Python loops as index arithmetic on the device (no track.npy round trip):
