@@ -19,6 +19,7 @@
  *   psfm_result_*           the list of Trajectory objects those functions return and the
  *                           id / min-length rule of main_connect_point_trajectories.py:56-60
  *   psfm_traj_augment       motion_seg/core/network/traj_oa_depth.py:72-114 augment_traj() (the classifier's 10-channel input)
+ *   psfm_traj_encode        motion_seg/core/network/traj_oa_depth.py:25-60 pt_transformer.forward() (joint_encoder, eval mode)
  *   psfm_labels_*           motion_seg/main_motion_segmentation.py:89-129 (per-window predictions -> labelled track.npy)
  *
  * Conventions
@@ -289,6 +290,40 @@ psfm_status psfm_window_sample(psfm_ctx* ctx, int frame0, int n_frames, int traj
  * pointer with k > 0, k < 0, n_frames < 1, h or w < 1, h*w or 10*k*n_frames above 2^31 - 1 (the kernel's 32-bit indices). */
 psfm_status psfm_traj_augment(psfm_ctx* ctx, const double* xy_norm, const double* mask_absent, const float* depth, int64_t k,
                               int n_frames, int h, int w, const float* kinv_host, float* out, void* stream);
+
+/* The motion classifier's trajectory transformer -- traj_oa_depth.joint_encoder(aug_trajs, masks) = pt_transformer.forward in eval
+ * mode (motion_seg/core/network/traj_oa_depth.py:25-60) -- from exactly what psfm_traj_augment and psfm_window_sample wrote:
+ * features [10][k][n_frames] f32, mask_absent (k,n_frames) f64 (padded where its .float() > 0.5).  out is the reference's [1,16,k]
+ * fp32 tensor (what it hands to the OANet decoder as feat.unsqueeze(-1)); the decoder and the sigmoid stay with the caller.
+ * Per trajectory, tokens l = 0 .. n_frames-1, fp32, dropout off:
+ *   x = relu(fc2(relu(input_fc1(f))))                                        two 1x1 convolutions, 10 -> 16 -> 16
+ *   encoder layer x 2 (post-norm): h = LN1(h + SA(h)); h = LN2(h + linear2(relu(linear1(h)))); memory = encoder.norm(h)
+ *   decoder layer x 2, starting again from x (the reference passes the same tensor as src and tgt):
+ *     d = LN1(d + SA(d)); d = LN2(d + CA(d, memory)); d = LN3(d + FFN(d));  out = max over ALL tokens of decoder.norm(d)
+ *   attention: 4 heads of width 4, q scaled by 1/2.  Keys at padded positions are masked in both SELF-attentions; queries at padded
+ *   positions are computed like any other; CROSS-attention attends to all memory positions, padded ones included (the reference
+ *   passes no memory_key_padding_mask); the max includes the padded tokens; no position is zeroed.  LayerNorm: biased variance,
+ *   eps 1e-5.
+ * Same formula, another summation order and another expf than torch's: results agree with the module's f64 evaluation as closely
+ * as the module's own fp32 run does (tests/golden/make_encoder_golden.py measures that error and derives the tests' bound from it).
+ * No result depends on k or on a trajectory's place among the k.  A trajectory whose positions are ALL padded (psfm_window_sample
+ * emits none) gets 16 unspecified values (NaN); every access stays in bounds and no other trajectory is affected.
+ * weights: psfm_traj_encode_weight_count() = 15872 floats on the DEVICE, the module's 68 parameters in its own state_dict order,
+ * every tensor row-major as stored ([out][in]):
+ *   input_fc1.weight [16][10], .bias [16]; fc2.weight [16][16], .bias [16];
+ *   transformer_model.encoder.layers.{0,1}: self_attn.in_proj_weight [48][16] (q, k, v), .in_proj_bias [48], self_attn.out_proj.weight
+ *     [16][16], .bias [16], linear1.weight [64][16], .bias [64], linear2.weight [16][64], .bias [16], norm1.weight, .bias, norm2.weight,
+ *     .bias [16] each                                                                                            (3280 per layer);
+ *   transformer_model.encoder.norm.weight, .bias;
+ *   transformer_model.decoder.layers.{0,1}: self_attn (as above), multihead_attn (the same four), linear1, linear2, norm1, norm2, norm3
+ *                                                                                                                (4400 per layer);
+ *   transformer_model.decoder.norm.weight, .bias.
+ * ASYNCHRONOUS: one launch on `stream`, no allocation, no host synchronisation.  k = 0 is a no-op.  PSFM_ERR_ARG, nothing launched:
+ * n_frames < 1 or n_frames > 64 (a trajectory lives inside one 64-lane wave), k < 0, 10*k*n_frames above 2^31 - 1 (the kernel's
+ * 32-bit indices), a NULL pointer with k > 0. */
+int psfm_traj_encode_weight_count(void);
+psfm_status psfm_traj_encode(psfm_ctx* ctx, const float* features, const double* mask_absent, const float* weights, int64_t k,
+                             int n_frames, float* out, void* stream);
 
 /* sfm/matches_from_flow.py:51-118 (traj_to_matches) from the saved set that psfm_result_filter left in HBM -- the
  * reference's per-trajectory Python loops as index arithmetic on the device (no track.npy round trip):

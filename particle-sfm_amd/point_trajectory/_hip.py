@@ -26,7 +26,7 @@ EXPORTS = [
     "psfm_path_consistency_eval", "psfm_sort_records",
     "psfm_shard_peer_area", "psfm_shard_peer_epoch", "psfm_shard_peer_open", "psfm_shard_peer_connect", "psfm_shard_solve_blocks", "psfm_shard_solve_peer",
     "psfm_labels_begin", "psfm_labels_merge_window", "psfm_labels_finish", "psfm_labels_device", "psfm_labels_copy", "psfm_labels_to_matches",
-    "psfm_traj_augment",
+    "psfm_traj_augment", "psfm_traj_encode_weight_count", "psfm_traj_encode",
 ]
 
 
@@ -103,6 +103,8 @@ def lib():
     L.psfm_window_sample.argtypes = [vp, i32, i32, i32, i32, i64, ctypes.c_uint64, i32, i32, i32, i32, i64, vp, vp, vp, vp,
                                      ctypes.POINTER(i64), vp]
     L.psfm_traj_augment.argtypes = [vp, vp, vp, vp, i64, i32, i32, i32, vp, vp, vp]
+    L.psfm_traj_encode_weight_count.argtypes = []
+    L.psfm_traj_encode.argtypes = [vp, vp, vp, vp, i64, i32, vp, vp]
     L.psfm_traj_to_matches.argtypes = [vp, i32, i32, vp, ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(i64), vp]
     L.psfm_matches_copy.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
     L.psfm_labels_begin.argtypes = [vp, vp]
