@@ -69,7 +69,7 @@
 // (its track died in an earlier step)
 #ifdef PSFM_PERSIST_CHECK
 // debug builds: bounds-check every lane-indexed store, remember the first offending site in ctr->pad
-#define PP_CHK(idx, lim, code) (((idx) >= 0 && (idx) < (lim)) ? true : (atomicCAS(&a.ctr->pad[0], 0, (code)), atomicMax(&a.ctr->pad[1], (int)(idx)), false))
+#define PP_CHK(idx, lim, code) (((idx) >= 0 && (idx) < (lim)) ? true : (atomicCAS(&psfm_cold()->ctr->pad[0], 0, (code)), atomicMax(&psfm_cold()->ctr->pad[1], (int)(idx)), false))
 #else
 #define PP_CHK(idx, lim, code) true
 #endif
@@ -78,12 +78,23 @@
 #endif
 #define PP_POOLED (-1)
 #define PP_PEND (-2)
+#define PP_DIED (-3)     // between its own step and section C of the same frame: the track died in THIS frame's step (PP_PEND from C on).
+                         // (A `live` flag held across E and the barrier instead was a 64-bit lane mask in two scalar registers.)
 
+// The kernel's arguments, in two parts: PsfmPersistArgs is what every wave needs in every frame, PsfmPersistCold what only a
+// thread 0, a dying track or the epilogue needs.  NEITHER is bound to registers for the loop: the kernel's one by-value
+// parameter is never named, and every use site reads its fields from the kernarg segment (s_load, scalar cache) through
+// psfm_hot() / psfm_cold(), whose empty asm keeps the loads at the use site.  A field thus occupies scalar registers from its
+// use site's load to its last use there, and what is derived from it (frame pointers, banded indices) is derived there.
+// (One 544-byte struct by value had the compiler keep ~136 dwords + the address arithmetic hoisted out of the frame loop
+// alive across it, in 78 SGPRs: 168 scalars spilled to VGPR lanes, 596 v_readlane sites, about a third of the VALU
+// instructions of a frame -- profiles/EXPERIMENTS.md section 12.  The same reason is behind psfm_bid() and the opaque
+// copies of t / tid / the phase-2 counts below: values that are cheap to recompute are recomputed, not held.)
 struct PsfmPersistArgs {
-    const float2* flows; const uint8_t* occ;   // (n_flows,H,W,2) f32 / n_flows maps of H*W u8, `occ_pitch` bytes apart
-    // fused flow_check (psfm_connect): the blocks compute the occlusion maps themselves, in the time they would spend
-    // waiting at the frame barriers, always at least three frames ahead of the step that samples them
-    const float2* flows_b; uint8_t* occ_w; float thres, t2; int fc; int fc_xcd_per;
+    const float2* flows; uint8_t* occ;         // (n_flows,H,W,2) f32 / n_flows maps of H*W u8, `occ_pitch` bytes apart
+    // fused flow_check (psfm_connect): the blocks compute the occlusion maps themselves (into `occ`), in the time they would
+    // spend waiting at the frame barriers, always at least three frames ahead of the step that samples them
+    const float2* flows_b; float t2; int fc; int fc_xcd_per;
     int xcd_per;                               // > 0: blocks below 8 * xcd_per own the lanes / grid points of block (b % 8) * xcd_per + b / 8 (see psfm_vblock)
     int64_t occ_pitch; PsfmFastDiv wdiv;
     int H, W; float cw, ch, rcw, rch;
@@ -91,44 +102,121 @@ struct PsfmPersistArgs {
     float2* dlog; int cap;                     // (n_flows, cap) sampled flow of every SURVIVED step: slab t, column = lane.  A
                                                // trajectory is its birth grid point plus the running f64 sum of its column's
                                                // entries (finalize re-runs the same additions); cap = gridDim.x * (256 + PP_GUESTS)
-    int cap_main;                              // gridDim.x * 256 thread lanes (columns [cap_main, cap) are the guests)
     uint8_t* maps;                             // 3 x G, 0/1, zeroed: marks of step t go to map t % 3
-    unsigned* survsh;                          // 2 x 64 words (128 B apart): frame+1 of the last step a block of the shard had a survivor in
+    unsigned long long* handoff;               // cap x 3: x bits, y bits, gi | (2*birth_frame + alive) << 32
+    unsigned* bar;                             // [0, 64) shard counters, [64] top counter, [65, 129) release flags; 32 words apart;
+                                               // behind them (PP_SURV) 2 x 64 words: frame+1 of the last step a block of the shard had a survivor in
+    int n_flows;
+    int nblk;                                  // gridDim.x (read from here: the implicit-argument pointer would be one more 64-bit value held across the loop)
+    PsfmFastDiv gwdiv, rdiv;                   // (rdiv: generic ratio only)
+};
+#define PP_SURV ((2 * PSFM_NSHARD + 1) * 32)   // first survivor word, in words from `bar`
+
+struct PsfmPersistCold {
+    int cap_main;                              // gridDim.x * 256 thread lanes (columns [cap_main, cap) are the guests)
+    int cap;
     PsfmCounters* ctr;
     PsfmShard* shards;                         // 2 x PSFM_NSHARD (free_top per parity set)
     int* free_stack; int free_cap; int nsh;   // nsh: free-lane stacks in use = min(PSFM_NSHARD, blocks)
-    unsigned long long* handoff;               // cap x 3: x bits, y bits, gi | (2*birth_frame + alive) << 32
     unsigned long long* fin_keys; int* fin_lanes;
     int seg_cap; int spill_base; int spill_cap;
     int2* seg_info;                            // per block: records, points
-    unsigned* bar;                             // [0, 64) shard counters, [64] top counter, [65, 129) release flags; 32 words apart
-    int n_flows, shift_b, shift_d;
-    PsfmFastDiv gwdiv, rdiv;
+    int shift_b, shift_d;
     int spin_limit;
 };
+struct PsfmPersistKernarg { PsfmPersistArgs hot; PsfmPersistCold cold; };   // the kernel's one parameter: `cold` at a known offset of the segment
 
-// what psfm_step_issue / psfm_step_finish / psfm_block_grid need for one frame
+typedef const __attribute__((address_space(4))) PsfmPersistArgs* PsfmHotPtr;
+typedef const __attribute__((address_space(4))) PsfmPersistCold* PsfmColdPtr;
+// The argument blocks, for ONE use site: the empty asm makes the address opaque there, so the loads behind it stay where they
+// are written (loop-invariant code motion would hoist them out of the frame loop and keep every field live across it)
+__device__ __forceinline__ PsfmHotPtr psfm_hot()
+{
+    const __attribute__((address_space(4))) char* k = (const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(k));
+    return (PsfmHotPtr)(k + offsetof(PsfmPersistKernarg, hot));
+}
+#define PA psfm_hot()
+// blockIdx.x for one use site (what is derived from it is then derived there, not hoisted in front of the frame loop and kept)
+__device__ __forceinline__ int psfm_bid()
+{
+    int b = (int)blockIdx.x;
+    asm volatile("" : "+s"(b));
+    return b;
+}
+#define PP_BID psfm_bid()
+#define PP_SHARD (psfm_bid() & (PSFM_NSHARD - 1))
+template <class P> __device__ __forceinline__ PsfmFastDiv psfm_fd(P p)
+{
+    PsfmFastDiv f;
+    f.m = p->m; f.sh1 = p->sh1; f.sh2 = p->sh2; f.d = 0u;
+    return f;
+}
+__device__ __forceinline__ PsfmColdPtr psfm_cold()
+{
+    const __attribute__((address_space(4))) char* k = (const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(k));
+    return (PsfmColdPtr)(k + offsetof(PsfmPersistKernarg, cold));
+}
+
+// what psfm_step_issue / psfm_step_finish need for one frame (live from the gathers to the blends) ...
 struct PsfmFrameView {
     const float2* flow; const uint8_t* occ;
     int H, W; float cw, ch, rcw, rch;
+};
+// ... and what a SURVIVED step needs behind them: psfm_block_grid's map of the frame and the frame's slab of the log
+struct PsfmMarksView {
     int ratio, GW, GH;
     uint8_t* blocked_cur; uint8_t stamp_cur;
     PsfmFastDiv rdiv;
+    float2* slab;
 };
 
-__device__ __forceinline__ void psfm_put_record(const PsfmPersistArgs& a, int slot, unsigned long long key, int lane)
+__device__ __forceinline__ PsfmFrameView psfm_frame_view(int t)
 {
+    const PsfmHotPtr a = psfm_hot();
+    PsfmFrameView v;
+    v.H = a->H; v.W = a->W; v.cw = a->cw; v.ch = a->ch; v.rcw = a->rcw; v.rch = a->rch;
+    v.flow = a->flows + (size_t)t * ((size_t)v.H * v.W); v.occ = a->occ + (size_t)t * a->occ_pitch;
+    return v;
+}
+// built where a step has survived, from the kernarg segment: held from the top of the frame these six scalars were spilled
+// across the flow_check slices in between
+template <int R>
+__device__ __forceinline__ PsfmMarksView psfm_marks_view(int t)
+{
+    const PsfmHotPtr a = psfm_hot();
+    PsfmMarksView m;
+    m.ratio = R > 0 ? R : a->ratio; m.GW = a->GW; m.GH = a->GH;
+    if (R > 0) { m.rdiv.m = 0u; m.rdiv.sh1 = 0; m.rdiv.sh2 = 0; m.rdiv.d = 0u; }
+    else m.rdiv = psfm_fd(&a->rdiv);
+    m.blocked_cur = a->maps + (size_t)(t % 3) * a->G; m.stamp_cur = 1;
+    m.slab = a->dlog + (size_t)t * a->cap;
+    return m;
+}
+
+__device__ __forceinline__ void psfm_put_record(int slot, unsigned long long key, int lane)
+{
+    const PsfmColdPtr c = psfm_cold();
+    const int seg_cap = c->seg_cap;
     int64_t o;
-    if (slot < a.seg_cap) {
-        o = (int64_t)blockIdx.x * a.seg_cap + slot;
+    if (slot < seg_cap) {
+        o = (int64_t)PP_BID * seg_cap + slot;
     } else {   // private segment full: shared tail
-        const int q = atomicAdd(&a.ctr->spill_cnt, 1);
-        if (q >= a.spill_cap) { atomicOr(&a.ctr->overflow, 2); return; }
-        o = (int64_t)a.spill_base + q;
+        PsfmCounters* ctr = c->ctr;
+        const int q = atomicAdd(&ctr->spill_cnt, 1);
+        if (q >= c->spill_cap) { atomicOr(&ctr->overflow, 2); return; }
+        o = (int64_t)c->spill_base + q;
     }
-    if (!PP_CHK(lane, a.cap, 6)) return;
-    a.fin_keys[o] = key;
-    a.fin_lanes[o] = lane;
+    if (!PP_CHK(lane, c->cap, 6)) return;
+    c->fin_keys[o] = key;
+    c->fin_lanes[o] = lane;
+}
+// key of a death record (the shifts are launch constants of the cold block)
+__device__ __forceinline__ unsigned long long psfm_cold_key(int last_time, int bf, int idx)
+{
+    const PsfmColdPtr c = psfm_cold();
+    return psfm_key(last_time, bf, idx, c->shift_b, c->shift_d);
 }
 
 // slots for `n_dead` records of this wave in the block's private segment (LDS counter, no global atomic)
@@ -159,31 +247,32 @@ extern "C" int psfm_debug_persist_timeline(int frame, unsigned long long* out_ho
 
 // ---- device-wide barrier #k (k = 0: prologue, k = t + 1: end of frame t).  Arrival: 64 shard counters -> the last
 // arriver of a shard bumps the top counter -> the last of those publishes k + 1 in 64 replicated release flags ----
-__device__ __forceinline__ void psfm_bar_arrive(const PsfmPersistArgs& a, int shard, int k, int lane)
+__device__ __forceinline__ void psfm_bar_arrive(int shard, int k, int lane)
 {
     int last = 0;
+    asm volatile("" : "+s"(k));   // (k + 1 is not to be shared with the frame's other multiples of t, computed a barrier earlier)
     if (lane == 0) {
-        const int nblk = (int)gridDim.x;
+        const int nblk = PA->nblk;
         const unsigned members = (unsigned)((nblk - shard + PSFM_NSHARD - 1) / PSFM_NSHARD);
-        const unsigned old = __hip_atomic_fetch_add(a.bar + shard * 32, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const unsigned old = __hip_atomic_fetch_add(PA->bar + shard * 32, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (old + 1 == members * (unsigned)(k + 1)) {
             const unsigned nsh = (unsigned)(nblk < PSFM_NSHARD ? nblk : PSFM_NSHARD);
-            const unsigned o2 = __hip_atomic_fetch_add(a.bar + 64 * 32, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const unsigned o2 = __hip_atomic_fetch_add(PA->bar + 64 * 32, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (o2 + 1 == nsh * (unsigned)(k + 1)) last = 1;
         }
     }
     last = __builtin_amdgcn_readfirstlane(last);
-    if (last) psfm_coh_st(a.bar + (65 + lane) * 32, (unsigned)(k + 1));
+    if (last) psfm_coh_st(PA->bar + (65 + lane) * 32, (unsigned)(k + 1));
 }
 // thread 0 only: spin until barrier #k is released; false = gave up / somebody else did
-__device__ __forceinline__ bool psfm_bar_wait(const PsfmPersistArgs& a, int shard, int k)
+__device__ __forceinline__ bool psfm_bar_wait(int shard, int k)
 {
-    const unsigned* flag = a.bar + (65 + shard) * 32;
+    const unsigned* flag = PA->bar + (65 + shard) * 32;
     int n = 0;
     while (psfm_coh_ld(flag) < (unsigned)(k + 1)) {
         __builtin_amdgcn_s_sleep(1);
-        if (++n > a.spin_limit) { atomicOr(&a.ctr->overflow, 8); psfm_coh_st(&a.ctr->abort, 1); return false; }
-        if ((n & 127) == 0 && psfm_coh_ld(&a.ctr->abort)) return false;
+        if (++n > psfm_cold()->spin_limit) { PsfmCounters* ctr = psfm_cold()->ctr; atomicOr(&ctr->overflow, 8); psfm_coh_st(&ctr->abort, 1); return false; }
+        if ((n & 127) == 0 && psfm_coh_ld(&psfm_cold()->ctr->abort)) return false;
     }
     return true;
 }
@@ -191,19 +280,22 @@ __device__ __forceinline__ bool psfm_bar_wait(const PsfmPersistArgs& a, int shar
 // ---- fused flow_check (utils.py:94-105): this thread's pixels of frame pair f.  Chunks of 1024 pixels, one per block
 // and round (block-strided over the map); a thread owns 4 pixels 256 apart, so every load / store instruction of a
 // wave is one contiguous run.  The mask bytes are written through: other XCDs sample them a few frames later ----
-__device__ __forceinline__ void psfm_fc_slice(const PsfmPersistArgs& a, int f, int tid)
+__device__ __forceinline__ void psfm_fc_slice(int f, int tid)
 {
-    const int P = a.H * a.W;
+    const PsfmHotPtr a = psfm_hot();   // (every field it needs is read here, per slice)
+    const int P = a->H * a->W;
     PsfmFcParams q;
-    q.H = a.H; q.W = a.W; q.cw = a.cw; q.ch = a.ch; q.rcw = a.rcw; q.rch = a.rch; q.thres = a.thres; q.t2 = a.t2;
-    const float2* __restrict__ F = a.flows + (size_t)f * P;
-    const float2* __restrict__ B = a.flows_b + (size_t)f * P;
-    uint8_t* O = a.occ_w + (size_t)f * a.occ_pitch;
-    // chunk -> block: XCD-aware when a.fc_xcd_per > 0 (block b runs on XCD b % 8 and takes chunk (b % 8) * per + b / 8 of every
+    q.H = a->H; q.W = a->W; q.cw = a->cw; q.ch = a->ch; q.rcw = a->rcw; q.rch = a->rch; q.thres = 0.f /* only the error-map form reads it */; q.t2 = a->t2;
+    const float2* __restrict__ F = a->flows + (size_t)f * P;
+    const float2* __restrict__ B = a->flows_b + (size_t)f * P;
+    uint8_t* O = a->occ + (size_t)f * a->occ_pitch;
+    // chunk -> block: XCD-aware when a->fc_xcd_per > 0 (block b runs on XCD b % 8 and takes chunk (b % 8) * per + b / 8 of every
     // round: each XCD covers one band of rows, so a row of B is gathered through ONE private L2 instead of two -- psfm_track.hip)
+    const PsfmFastDiv wdiv = psfm_fd(&a->wdiv);
+    const int W = a->W;
     const int nch = (P + 1023) / 1024;
-    const int per = a.fc_xcd_per;
-    for (int q0 = blockIdx.x; q0 < (per > 0 ? 8 * per : nch); q0 += gridDim.x) {
+    const int per = a->fc_xcd_per, nblk = a->nblk;
+    for (int q0 = PP_BID; q0 < (per > 0 ? 8 * per : nch); q0 += nblk) {
         const int ci = per > 0 ? (q0 & 7) * per + (q0 >> 3) : q0;
         if (ci >= nch) continue;
         const int p0 = ci * 1024 + tid;
@@ -213,7 +305,7 @@ __device__ __forceinline__ void psfm_fc_slice(const PsfmPersistArgs& a, int f, i
             const int p = p0 + k * 256;
             fv[k] = p < P ? psfm_ld(F, (unsigned)p * 8u) : make_float2(0.f, 0.f);
         }
-        int y = (int)psfm_fastdiv((unsigned)p0, a.wdiv), x = p0 - y * a.W;
+        int y = (int)psfm_fastdiv((unsigned)p0, wdiv), x = p0 - y * W;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const int p = p0 + k * 256;
@@ -233,7 +325,7 @@ __device__ __forceinline__ void psfm_fc_slice(const PsfmPersistArgs& a, int f, i
 #endif
             psfm_coh_st(O + p, o);
             x += 256;
-            while (x >= a.W) { x -= a.W; ++y; }
+            while (x >= W) { x -= W; ++y; }
         }
     }
 }
@@ -244,10 +336,10 @@ __device__ __forceinline__ void psfm_fc_slice(const PsfmPersistArgs& a, int f, i
 // is pulled through two L2s: 31.0 MB of reads per step counted at the fabric for 19.2 MB of taps (profiles/r04_o_*).  Banded like
 // flow_check's chunks (block b -> virtual block (b % 8) * per + b / 8), an XCD owns one band of grid rows.  Blocks beyond the grid's
 // (spare lanes only) keep their own index; ids do not depend on which lane hosts which track.
-__device__ __forceinline__ int psfm_vblock(const PsfmPersistArgs& a)
+__device__ __forceinline__ int psfm_vblock()
 {
-    const int b = (int)blockIdx.x;
-    return (a.xcd_per > 0 && b < 8 * a.xcd_per) ? (b & 7) * a.xcd_per + (b >> 3) : b;
+    const int b = PP_BID, per = PA->xcd_per;
+    return (per > 0 && b < 8 * per) ? (b & 7) * per + (b >> 3) : b;
 }
 
 // entry k of the phase-2 list: kind 1 newborn (ex = grid index, host = local PEND thread or -1), kind 2 adopted
@@ -255,7 +347,7 @@ __device__ __forceinline__ int psfm_vblock(const PsfmPersistArgs& a)
 struct PsfmEntry { int kind, ex, host; };
 
 template <int R>
-__global__ __launch_bounds__(PP_BLOCK) PP_WAVES void psfm_chain_persist_kernel(PsfmPersistArgs a)
+__global__ __launch_bounds__(PP_BLOCK) PP_WAVES void psfm_chain_persist_kernel(PsfmPersistKernarg)   // read through psfm_hot() / psfm_cold() only
 {
     __shared__ int s_births[PP_NW], s_adopt[PP_NW], s_pend[PP_NW];
     __shared__ int s_new_g[PP_BLOCK];       // grid index of the births, one 64-slot segment per wave
@@ -263,7 +355,7 @@ __global__ __launch_bounds__(PP_BLOCK) PP_WAVES void psfm_chain_persist_kernel(P
     __shared__ int s_pend_tid[PP_BLOCK];    // threads whose track died in the previous step, same layout
     __shared__ double2 s_xp[PP_BLOCK];      // exchange slots indexed by the OWNER thread: position in / out
     __shared__ int s_xg[PP_BLOCK];          // ... birth grid index
-    __shared__ int s_xf[PP_BLOCK];          // ... 0 nothing, 1 track alive (take it), 2 track died in its step
+    __shared__ int s_xf[PP_BLOCK];          // ... 0 nothing, 1 newborn alive (take it), 3 adopted track alive (take it), 2 track died in its step
     __shared__ int s_gi[PP_BLOCK];          // birth grid index of the thread's live track (only needed when it dies)
     __shared__ int s_npts[PP_BLOCK];        // trajectory points written by the thread
     __shared__ int s_seg_start[PP_PROBE + 1], s_seg_end[PP_PROBE + 1];
@@ -274,10 +366,8 @@ __global__ __launch_bounds__(PP_BLOCK) PP_WAVES void psfm_chain_persist_kernel(P
     __shared__ int s_glive[PP_GUESTS], s_gfree[PP_GUESTS], s_nglive, s_ngfree;   // this frame's live / free slots
 
     int tid = threadIdx.x;
-    int L = psfm_vblock(a) * PP_BLOCK + tid;
-    const int ratio = R > 0 ? R : a.ratio;
-    const int shard = blockIdx.x % PSFM_NSHARD;
-    const size_t P = (size_t)a.H * a.W;
+    int L = psfm_vblock() * PP_BLOCK + tid;
+    const int ratio = R > 0 ? R : PA->ratio;
 
     // (the per-thread indices are re-derived from `tid` at the top of every frame: values hoisted out of the frame loop
     // cost registers for its whole body, and this kernel must fit 64 VGPRs for 8 blocks per CU)
@@ -287,8 +377,9 @@ __global__ __launch_bounds__(PP_BLOCK) PP_WAVES void psfm_chain_persist_kernel(P
     double2 p = make_double2(0.0, 0.0);
     s_gi[tid] = L;
     s_npts[tid] = 0;
-    if (L < a.G) {
-        const int gy = (int)psfm_fastdiv((unsigned)L, a.gwdiv), gx = L - gy * a.GW;
+    if (L < PA->G) {
+        const PsfmHotPtr a = psfm_hot();
+        const int gy = (int)psfm_fastdiv((unsigned)L, psfm_fd(&a->gwdiv)), gx = L - gy * a->GW;
         p = make_double2((double)(gx * ratio), (double)(gy * ratio));
         bf = 0;
         s_npts[tid] = 1;
@@ -298,27 +389,24 @@ __global__ __launch_bounds__(PP_BLOCK) PP_WAVES void psfm_chain_persist_kernel(P
     if (tid == 0) { s_rec_cnt = 0; s_alive_any[0] = 0; s_alive_any[1] = 0; s_done = 0; }
     // ---- prologue: the occlusion maps of the first two frame pairs, then barrier #0 ----
     int fc_next = 0;     // (per wave) frame pairs whose occlusion map this wave has finished its share of
-    if (a.fc) {
-        for (; fc_next < 2 && fc_next < a.n_flows; ++fc_next) psfm_fc_slice(a, fc_next, tid);
+    if (PA->fc) {
+        for (; fc_next < 2 && fc_next < PA->n_flows; ++fc_next) psfm_fc_slice(fc_next, tid);
         __builtin_amdgcn_s_waitcnt(0);
     }
     __syncthreads();
-    if (tid / PSFM_WAVE == PP_NW - 1) psfm_bar_arrive(a, shard, 0, tid & (PSFM_WAVE - 1));
-    if (a.fc) {   // step 0 samples map 0 ahead of its barrier wait: every block's share of it must be in HBM first
-        if (tid == 0) s_ok = psfm_bar_wait(a, shard, 0) ? 1 : 0;
+    if (tid / PSFM_WAVE == PP_NW - 1) psfm_bar_arrive(PP_SHARD, 0, tid & (PSFM_WAVE - 1));
+    if (PA->fc) {   // step 0 samples map 0 ahead of its barrier wait: every block's share of it must be in HBM first
+        if (tid == 0) s_ok = psfm_bar_wait(PP_SHARD, 0) ? 1 : 0;
         __syncthreads();
         if (!s_ok) return;
     }
 
-    for (int t = 0; t < a.n_flows; ++t) {
+    for (int t = 0; t < PA->n_flows; ++t) {
         asm volatile("" : "+v"(tid));
-        L = psfm_vblock(a) * PP_BLOCK + tid;
+        L = psfm_vblock() * PP_BLOCK + tid;
         const int lane = tid & (PSFM_WAVE - 1), wave = tid / PSFM_WAVE;
-        PsfmFrameView v;
-        v.flow = a.flows + (size_t)t * P; v.occ = a.occ + (size_t)t * a.occ_pitch;
-        v.H = a.H; v.W = a.W; v.cw = a.cw; v.ch = a.ch; v.rcw = a.rcw; v.rch = a.rch; v.ratio = a.ratio; v.GW = a.GW; v.GH = a.GH; v.rdiv = a.rdiv;
-        v.blocked_cur = a.maps + (size_t)(t % 3) * a.G; v.stamp_cur = 1;
-        float2* dlog_t = a.dlog + (size_t)t * a.cap;
+        // this frame's uniforms, from the kernarg segment: nothing of them is carried from frame to frame, nor across the barrier wait
+        PsfmFrameView v = psfm_frame_view(t);
         const int cur = t & 1, prev = cur ^ 1;
 
         PP_TL(0);
@@ -326,21 +414,22 @@ __global__ __launch_bounds__(PP_BLOCK) PP_WAVES void psfm_chain_persist_kernel(P
         bool any_alive = false;          // a track of this thread survived step t
         int npts = 0;
         // one step (s = t or t + 1) of this thread's own track from the gathered taps `ld`: log entry, marks, or the death record
-        auto own_step = [&](const PsfmFrameView& vs, float2* slab, int s, const PsfmStepLoads& ld, bool mine, bool& alive_any) {
+        auto own_step = [&](const PsfmFrameView& vs, int s, const PsfmStepLoads& ld, bool mine, bool& alive_any) {
             PsfmStep s1;
             s1.alive = true;
             if (mine) s1 = psfm_step_finish(vs, p, ld);
             const int slot1 = psfm_record_slot(&s_rec_cnt, !s1.alive);
             if (mine) {
                 if (s1.alive) {
-                    if (PP_CHK(L, a.cap, 1)) slab[L] = s1.flow;
-                    psfm_block_grid<R, PP_COH_MARKS>(vs, (int)s1.next.x, (int)s1.next.y);
+                    const PsfmMarksView m = psfm_marks_view<R>(s);
+                    if (PP_CHK(L, PA->cap, 1)) m.slab[L] = s1.flow;
+                    psfm_block_grid<R, PP_COH_MARKS>(m, (int)s1.next.x, (int)s1.next.y);
                     p = s1.next;
                     alive_any = true;
                     ++npts;
                 } else {
-                    psfm_put_record(a, slot1, psfm_key(s, bf, s_gi[tid], a.shift_b, a.shift_d), L);
-                    bf = PP_PEND;       // free from the next frame on (`live` keeps it out of this frame's PEND list)
+                    psfm_put_record(slot1, psfm_cold_key(s, bf, s_gi[tid]), L);
+                    bf = PP_DIED;       // free from the next frame on (kept out of this frame's PEND list)
                     p = make_double2(0.0, 0.0);
                 }
             }
@@ -351,23 +440,24 @@ __global__ __launch_bounds__(PP_BLOCK) PP_WAVES void psfm_chain_persist_kernel(P
         // ---- E: the live tracks' own step.  It needs nothing from other blocks, and its marks go to a map nobody reads
         // before barrier t (three maps), so the first PP_PRE_WAVES waves run it BEFORE waiting for barrier t-1 (their
         // ALU hides under the barrier latency) and the others behind the loads of C (under that round trip) ----
-        auto do_E = [&]() { own_step(v, dlog_t, t, l1, live, any_alive); };
+        auto do_E = [&]() { own_step(v, t, l1, live, any_alive); };
         // (letting a block that finds barrier t-1 already released skip ahead and run E behind C made no difference)
         const bool e_first = wave < PP_PRE_WAVES;
         if (e_first) do_E();
 
         // ---- B: barrier #t (end of frame t-1; #0 = prologue).  While it is not released the waves work ahead on the
         //      occlusion maps (each wave for itself: a slice has no LDS and no block barrier in it) ----
-        if (a.fc) {
-            const unsigned* flag = a.bar + (65 + shard) * 32;
-            const int fc_lim = t + PP_FC_AHEAD < a.n_flows ? t + PP_FC_AHEAD : a.n_flows;
+        if (PA->fc) {
+            const PsfmHotPtr a = psfm_hot();
+            const unsigned* flag = a->bar + (65 + PP_SHARD) * 32;
+            const int nf = a->n_flows, fc_lim = t + PP_FC_AHEAD < nf ? t + PP_FC_AHEAD : nf;
             while (fc_next < fc_lim) {
                 if (__builtin_amdgcn_readfirstlane((int)psfm_coh_ld(flag)) >= t + 1 || (PP_WHATIF & 32)) break;
-                psfm_fc_slice(a, fc_next, tid);
+                psfm_fc_slice(fc_next, tid);
                 ++fc_next;
             }
         }
-        if (tid == 0) s_ok = (PP_WHATIF & 4) ? 1 : (psfm_bar_wait(a, shard, t) ? 1 : 0);
+        if (tid == 0) s_ok = (PP_WHATIF & 4) ? 1 : (psfm_bar_wait(PP_SHARD, t) ? 1 : 0);
         __syncthreads();
         if (!s_ok) return;
 
@@ -377,19 +467,22 @@ __global__ __launch_bounds__(PP_BLOCK) PP_WAVES void psfm_chain_persist_kernel(P
         PP_TL(1);
         // ---- C (issue): respawn byte, survivor flag, hand-off slot -- consumed after E, which runs under their latency ----
         const bool poll = t > 0 && bf == PP_POOLED && !(PP_WHATIF & 8);
-        const bool gridpt = t > 0 && L < a.G && !(PP_WHATIF & 8);
-        uint8_t* map_prev = a.maps + (size_t)((t + 2) % 3) * a.G;   // marks of step t-1; cleared here, written again at t+2
+        const PsfmHotPtr ac = psfm_hot();
+        const int G = ac->G;
+        const bool gridpt = t > 0 && L < G && !(PP_WHATIF & 8);
+        uint8_t* map_prev = ac->maps + (size_t)((t + 2) % 3) * G;   // marks of step t-1; cleared here, written again at t+2
         unsigned sv = 0, byte = 0;
         unsigned long long h0 = 0, h1 = 0, h2 = ~0ull;
         // "did any track survive step t-1?" only matters to grid point 0 (see below): one wave reads the 64 shard words.
         // (One flag word read by every thread would queue half a million L2-bypassing loads on one memory channel.)
-        if (t > 0 && blockIdx.x == 0 && tid < PSFM_NSHARD) sv = psfm_coh_ld(a.survsh + (prev * PSFM_NSHARD + tid) * 32);
+        if (t > 0 && PP_BID == 0 && tid < PSFM_NSHARD) sv = psfm_coh_ld(ac->bar + PP_SURV + (prev * PSFM_NSHARD + tid) * 32);
         if (gridpt) byte = psfm_coh_ld(map_prev + L);
         if (poll) {
-            const unsigned long long* h = a.handoff + (size_t)L * 3;
+            const unsigned long long* h = ac->handoff + (size_t)L * 3;
             h0 = psfm_coh_ld(h); h1 = psfm_coh_ld(h + 1); h2 = psfm_coh_ld(h + 2);
         }
 
+        v = psfm_frame_view(t);   // (again: held across the flow_check slices of the wait, part of it was spilled)
         if (!e_first) do_E();
 
         // ---- C (consume): respawn test, adoption ----
@@ -400,7 +493,10 @@ __global__ __launch_bounds__(PP_BLOCK) PP_WAVES void psfm_chain_persist_kernel(P
             birth = byte == 0;
             // No survivor at all: nothing is marked, every grid point respawns -- except that SciPy's EDT then measures
             // to a phantom feature at (y=-1, x=0): (cy+1)^2 + cx^2 > r^2 fails at grid point 0 only (1 > r^2 is false).
-            if (L == 0 && svm == 0ull) birth = ((0 + 1) * (0 + 1) + 0 * 0) > ratio * ratio;
+            if (L == 0 && svm == 0ull) {
+                const int r0 = R > 0 ? R : PA->ratio;     // (read here: the generic kernel held the hoisted comparison in a spilled mask)
+                birth = ((0 + 1) * (0 + 1) + 0 * 0) > r0 * r0;
+            }
             if (PP_WHATIF & 1) birth = false;
         }
         bool adopted = false;
@@ -416,7 +512,8 @@ __global__ __launch_bounds__(PP_BLOCK) PP_WAVES void psfm_chain_persist_kernel(P
                 }
             }
         }
-        const bool pend = (bf == PP_PEND) & !live;
+        const bool pend = bf == PP_PEND;
+        if (bf == PP_DIED) bf = PP_PEND;
         const unsigned long long bm = __ballot(birth), am = __ballot(adopted), pm = __ballot(pend);
         if (lane == 0) { s_births[wave] = __popcll(bm); s_adopt[wave] = __popcll(am); s_pend[wave] = __popcll(pm); }
         if (birth) s_new_g[wave * PSFM_WAVE + psfm_rank_in(bm)] = L;
@@ -443,9 +540,16 @@ __global__ __launch_bounds__(PP_BLOCK) PP_WAVES void psfm_chain_persist_kernel(P
         const int ngl = s_nglive;
         const int gmatched = (nb - matched) < s_ngfree ? (nb - matched) : s_ngfree;   // ... by its free guest lanes
         const int n2 = nb + nad + ngl;
+        const int t_frame = t, nb_f = __builtin_amdgcn_readfirstlane(nb), nad_f = __builtin_amdgcn_readfirstlane(nad), npd_f = __builtin_amdgcn_readfirstlane(npd),
+                  matched_f = __builtin_amdgcn_readfirstlane(matched), gmatched_f = __builtin_amdgcn_readfirstlane(gmatched);   // (block-uniform: sums of LDS words)
 
         // ---- D/E: phase-2 steps in passes of one entry per thread (a second pass only after a mass respawn) ----
         for (int base = 0; base == 0 || base < n2; base += PP_BLOCK) {
+            // (opaque copies: what the pass derives from the frame's counts and its number is derived in the pass -- hoisted in
+            // front of this loop it was some twenty-five scalars written to and read back from VGPR lanes in every frame)
+            int t = t_frame, nb = nb_f, nad = nad_f, npd = npd_f, matched = matched_f, gmatched = gmatched_f;
+            asm volatile("" : "+s"(t), "+s"(nb), "+s"(nad), "+s"(npd), "+s"(matched), "+s"(gmatched));
+            const int cur = t & 1, prev = cur ^ 1;
             const int k = base + tid;
             PsfmEntry e;
             e.kind = 0; e.ex = -1; e.host = -1;
@@ -477,7 +581,8 @@ __global__ __launch_bounds__(PP_BLOCK) PP_WAVES void psfm_chain_persist_kernel(P
             if (e.kind != 0) {
                 double2 q;
                 if (e.kind == 1) {
-                    const int gy = (int)psfm_fastdiv((unsigned)e.ex, a.gwdiv), gx = e.ex - gy * a.GW;
+                    const PsfmHotPtr a = psfm_hot();
+                    const int gy = (int)psfm_fastdiv((unsigned)e.ex, psfm_fd(&a->gwdiv)), gx = e.ex - gy * a->GW;
                     q = make_double2((double)(gx * ratio), (double)(gy * ratio));
                 } else if (e.kind == 2) {
                     q = s_xp[e.ex];
@@ -488,17 +593,19 @@ __global__ __launch_bounds__(PP_BLOCK) PP_WAVES void psfm_chain_persist_kernel(P
             }
 #ifdef PSFM_TIMELINE
             if (base == 0 && tid == 0 && t == g_pp_tl_frame) {
-                int* st = g_pp_st + blockIdx.x * 8;
+                int* st = g_pp_st + PP_BID * 8;
                 st[0] = nb; st[1] = nad; st[2] = npd; st[3] = ngl; st[4] = s_ngfree; st[5] = nb - matched - gmatched; st[6] = npd - matched - PP_KEEP;
             }
 #endif
             if (base == 0 && tid == 0) {
-                PsfmShard* sh_pop = a.shards + cur * PSFM_NSHARD;
-                PsfmShard* sh_push = a.shards + prev * PSFM_NSHARD;
+                const PsfmColdPtr c = psfm_cold();
+                const int nsh = c->nsh, free_cap = c->free_cap;
+                PsfmShard* sh_pop = c->shards + cur * PSFM_NSHARD;
+                PsfmShard* sh_push = c->shards + prev * PSFM_NSHARD;
                 int need = nb - matched - gmatched; // births that must pop a lane
                 const int n_push = npd - matched - PP_KEEP;   // free lanes beyond the block's own reserve go to the global stacks
                 int bfree = 0;
-                const int fsh = blockIdx.x % a.nsh;   // (the barrier keeps its own 64 shards)
+                const int fsh = PP_BID % nsh;   // (the barrier keeps its own 64 shards)
                 if (n_push > 0) bfree = atomicAdd(&sh_push[fsh].free_top, n_push);
                 int nseg = 0, done = 0;
                 // pops: rounds of four independent atomics (own shard first), one round trip per round.  The request is
@@ -510,7 +617,7 @@ __global__ __launch_bounds__(PP_BLOCK) PP_WAVES void psfm_chain_persist_kernel(P
                     int sh[4], ask[4], old[4];
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
-                        sh[j] = (fsh + (rd * 4 + j) * 7) % a.nsh;
+                        sh[j] = (fsh + (rd * 4 + j) * 7) % nsh;
                         ask[j] = q4 + (j < r4 ? 1 : 0);
                         old[j] = ask[j] > 0 ? atomicSub(&sh_pop[sh[j]].free_top, ask[j]) : 0;
                     }
@@ -519,7 +626,7 @@ __global__ __launch_bounds__(PP_BLOCK) PP_WAVES void psfm_chain_persist_kernel(P
                         const int take = old[j] < 0 ? 0 : (old[j] > ask[j] ? ask[j] : old[j]);
                         if (take < ask[j]) atomicAdd(&sh_pop[sh[j]].free_top, ask[j] - take);
                         if (take > 0) {
-                            s_seg_start[nseg] = sh[j] * a.free_cap + old[j] - 1;   // rank q of the segment -> entry start - q
+                            s_seg_start[nseg] = sh[j] * free_cap + old[j] - 1;   // rank q of the segment -> entry start - q
                             done += take;
                             s_seg_end[nseg] = done;
                             ++nseg;
@@ -529,7 +636,7 @@ __global__ __launch_bounds__(PP_BLOCK) PP_WAVES void psfm_chain_persist_kernel(P
                 }
                 s_base_free = bfree;
                 if (need > 0) {
-                    const int base_new = atomicAdd(&a.ctr->n_lanes, need);
+                    const int base_new = atomicAdd(&c->ctr->n_lanes, need);
                     s_seg_start[nseg] = -(base_new + 1);   // negative: fresh lanes base_new, base_new+1, ...
                     done += need;
                     s_seg_end[nseg] = done;
@@ -547,10 +654,12 @@ __global__ __launch_bounds__(PP_BLOCK) PP_WAVES void psfm_chain_persist_kernel(P
                 if (pend) {
                     const int r = my_pend_before + psfm_rank_in(pm);
                     if (r >= matched + PP_KEEP) {
-                        int* free_push = a.free_stack + (size_t)prev * a.free_cap * PSFM_NSHARD;
+                        const PsfmColdPtr c = psfm_cold();
+                        const int free_cap = c->free_cap;
+                        int* free_push = c->free_stack + (size_t)prev * free_cap * PSFM_NSHARD;
                         const int fpos = s_base_free + (r - matched - PP_KEEP);
-                        if (fpos < a.free_cap && PP_CHK(fpos, a.free_cap, 7)) psfm_coh_st(free_push + (size_t)(blockIdx.x % a.nsh) * a.free_cap + fpos, L);
-                        else atomicOr(&a.ctr->overflow, 1);
+                        if (fpos < free_cap && PP_CHK(fpos, free_cap, 7)) psfm_coh_st(free_push + (size_t)(PP_BID % c->nsh) * free_cap + fpos, L);
+                        else atomicOr(&c->ctr->overflow, 1);
                         bf = PP_POOLED;
                     }
                 }
@@ -564,62 +673,66 @@ __global__ __launch_bounds__(PP_BLOCK) PP_WAVES void psfm_chain_persist_kernel(P
                 double2 q;
                 int bfk, gik, col, gs = -1;      // birth frame, birth grid index, log column (= lane) of the entry's track
                 if (e.kind == 1) {
-                    const int gy = (int)psfm_fastdiv((unsigned)e.ex, a.gwdiv), gx = e.ex - gy * a.GW;
+                    const PsfmHotPtr a = psfm_hot();
+                    const int gy = (int)psfm_fastdiv((unsigned)e.ex, psfm_fd(&a->gwdiv)), gx = e.ex - gy * a->GW;
                     q = make_double2((double)(gx * ratio), (double)(gy * ratio));
                     bfk = t; gik = e.ex;
                     // lane of the newborn: the block's k-th PEND lane, else a free guest lane, else a popped / fresh lane
                     if (k < matched) {
-                        col = psfm_vblock(a) * PP_BLOCK + e.host;
+                        col = psfm_vblock() * PP_BLOCK + e.host;
                     } else if (k < matched + gmatched) {
                         gs = s_gfree[k - matched];
-                        col = a.cap_main + blockIdx.x * PP_GUESTS + gs;
+                        col = psfm_cold()->cap_main + PP_BID * PP_GUESTS + gs;
                     } else {
-                        const int* free_pop = a.free_stack + (size_t)cur * a.free_cap * PSFM_NSHARD;
+                        const PsfmColdPtr c = psfm_cold();
+                        const int* free_pop = c->free_stack + (size_t)cur * c->free_cap * PSFM_NSHARD;
                         const int qq = k - matched - gmatched;
                         int j = 0, pv = 0;
                         while (j < s_nseg - 1 && qq >= s_seg_end[j]) { pv = s_seg_end[j]; ++j; }
                         const int st = s_seg_start[j];
-                        if (st >= 0) (void)PP_CHK(st - (qq - pv), 2 * a.free_cap * PSFM_NSHARD, 9);
+                        if (st >= 0) (void)PP_CHK(st - (qq - pv), 2 * c->free_cap * PSFM_NSHARD, 9);
                         col = st >= 0 ? psfm_coh_ld(free_pop + (st - (qq - pv))) : (-(st + 1) + (qq - pv));
-                        if (col >= a.cap_main) col = -1;
+                        if (col >= c->cap_main) col = -1;
                     }
                 } else if (e.kind == 2) {
                     q = s_xp[e.ex];
                     bfk = t - 1; gik = s_xg[e.ex];
-                    col = psfm_vblock(a) * PP_BLOCK + e.ex;
+                    col = psfm_vblock() * PP_BLOCK + e.ex;
                 } else {
                     q = s_gp[e.ex];
                     bfk = s_gbf[e.ex]; gik = s_ggi[e.ex];
-                    col = a.cap_main + blockIdx.x * PP_GUESTS + e.ex;
+                    col = psfm_cold()->cap_main + PP_BID * PP_GUESTS + e.ex;
                 }
                 if (col >= 0) {
-                    (void)PP_CHK(col, a.cap, 2);
+                    (void)PP_CHK(col, PA->cap, 2);
                     const PsfmStep s2 = psfm_step_finish(v, q, l2);
                     if (e.kind == 1) ++npts;                  // the birth point itself
                     if (s2.alive) {
-                        if (PP_CHK(col, a.cap, 3)) dlog_t[col] = s2.flow;
-                        psfm_block_grid<R, PP_COH_MARKS>(v, (int)s2.next.x, (int)s2.next.y);
+                        const PsfmMarksView m = psfm_marks_view<R>(t);
+                        if (PP_CHK(col, PA->cap, 3)) m.slab[col] = s2.flow;
+                        psfm_block_grid<R, PP_COH_MARKS>(m, (int)s2.next.x, (int)s2.next.y);
                         any_alive = true;
                         ++npts;
                     } else {   // (a newborn lost in its first step is a length-1 trajectory)
                         const int slot = atomicAdd(&s_rec_cnt, 1);
-                        psfm_put_record(a, slot, psfm_key(t, bfk, gik, a.shift_b, a.shift_d), col);
+                        psfm_put_record(slot, psfm_cold_key(t, bfk, gik), col);
                     }
                     // ---- where the track lives from here on ----
                     if (e.kind == 1) {
                         const bool popped = k >= matched + gmatched;
-                        if (popped && s2.alive && t == a.n_flows - 1) {
+                        const int nf = PA->n_flows;
+                        if (popped && s2.alive && t == nf - 1) {
                             // born in the last frame on a popped lane: its owner never gets to adopt it, so the
                             // "still active at the end" record (last valid time n_flows) is written here
                             const int slot = atomicAdd(&s_rec_cnt, 1);
-                            psfm_put_record(a, slot, psfm_key(a.n_flows, t, e.ex, a.shift_b, a.shift_d), col);
+                            psfm_put_record(slot, psfm_cold_key(nf, t, e.ex), col);
                         }
                         if (k < matched) {
                             s_xp[e.host] = s2.next; s_xg[e.host] = e.ex; s_xf[e.host] = s2.alive ? 1 : 2;
                         } else if (gs >= 0) {
                             if (s2.alive) { s_gp[gs] = s2.next; s_ggi[gs] = e.ex; s_gbf[gs] = t; }
-                        } else if (PP_CHK(col, a.cap_main, 8)) {
-                            unsigned long long* h = a.handoff + (size_t)col * 3;
+                        } else if (PP_CHK(col, psfm_cold()->cap_main, 8)) {
+                            unsigned long long* h = PA->handoff + (size_t)col * 3;
                             psfm_coh_st(h, (unsigned long long)__double_as_longlong(s2.next.x));
                             psfm_coh_st(h + 1, (unsigned long long)__double_as_longlong(s2.next.y));
                             psfm_coh_st(h + 2, (unsigned long long)(unsigned)e.ex |
@@ -627,17 +740,18 @@ __global__ __launch_bounds__(PP_BLOCK) PP_WAVES void psfm_chain_persist_kernel(P
                         }
                     } else if (e.kind == 2) {
                         if (s2.alive) s_xp[e.ex] = s2.next;
-                        s_xf[e.ex] = s2.alive ? 1 : 2;
+                        s_xf[e.ex] = s2.alive ? 3 : 2;
                     } else {
                         if (s2.alive) s_gp[e.ex] = s2.next;
                         else s_gbf[e.ex] = -1;   // free from the next frame on (this frame's free list is already fixed)
                     }
                 } else {
-                    atomicOr(&a.ctr->overflow, 4);   // more tracks than resident lanes: the per-frame path takes over
+                    atomicOr(&psfm_cold()->ctr->overflow, 4);   // more tracks than resident lanes: the per-frame path takes over
                 }
             }
         }
         PP_TL(5);
+        asm volatile("" : "+s"(t), "+v"(tid));   // (t & 1, t - 1, tid == 0 below: from t and tid, not held across the passes)
         if (npts) s_npts[tid] += npts;
         const unsigned long long alm = __ballot(any_alive);
         if (lane == 0 && alm != 0ull) s_alive_any[t & 1] = 1;   // benign race: every writer stores 1
@@ -647,8 +761,8 @@ __global__ __launch_bounds__(PP_BLOCK) PP_WAVES void psfm_chain_persist_kernel(P
             const int f = s_xf[tid];
             if (f != 0) {
                 s_xf[tid] = 0;
-                if (f == 1) {
-                    bf = adopted ? t - 1 : t;   // adopted: born at t-1 in the block that popped this lane; else hosted newborn
+                if (f != 2) {
+                    bf = f == 3 ? t - 1 : t;    // 3 = adopted: born at t-1 in the block that popped this lane; 1 = hosted newborn
                     s_gi[tid] = s_xg[tid];
                     p = s_xp[tid];
                 } else {
@@ -656,13 +770,13 @@ __global__ __launch_bounds__(PP_BLOCK) PP_WAVES void psfm_chain_persist_kernel(P
                 }
             }
         }
-        if (tid == 0 && s_alive_any[t & 1]) { psfm_coh_st(a.survsh + (cur * PSFM_NSHARD + shard) * 32, (unsigned)(t + 1)); s_alive_any[t & 1] = 0; }
+        if (tid == 0 && s_alive_any[t & 1]) { psfm_coh_st(PA->bar + PP_SURV + ((t & 1) * PSFM_NSHARD + PP_SHARD) * 32, (unsigned)(t + 1)); s_alive_any[t & 1] = 0; }
         // ---- F: everything this block wrote is acknowledged -> arrive ----
         // (a step samples the occlusion map of its frame as early as right after the previous arrival, when only the
         // barrier before that one is known to be complete: maps up to t+2 must be finished before arriving at #t+1)
-        if (a.fc) {
-            const int need = t + 3 < a.n_flows ? t + 3 : a.n_flows;
-            if (!(PP_WHATIF & 16)) for (; fc_next < need; ++fc_next) psfm_fc_slice(a, fc_next, tid);
+        if (PA->fc) {
+            const int nf = PA->n_flows, need = t + 3 < nf ? t + 3 : nf;
+            if (!(PP_WHATIF & 16)) for (; fc_next < need; ++fc_next) psfm_fc_slice(fc_next, tid);
         }
         // ---- F: arrive.  No block barrier in front of it: a wave whose stores are acknowledged counts itself in (LDS) and
         //      goes on to the next frame; the wave that comes last arrives for the block ----
@@ -675,7 +789,7 @@ __global__ __launch_bounds__(PP_BLOCK) PP_WAVES void psfm_chain_persist_kernel(P
             if (last_wave) {
                 if (lane == 0) s_done = 0;
                 PP_TL(7);
-                psfm_bar_arrive(a, shard, t + 1, lane);
+                psfm_bar_arrive(PP_SHARD, t + 1, lane);
             }
         }
 #ifndef PP_NO_SETPRIO
@@ -686,13 +800,14 @@ __global__ __launch_bounds__(PP_BLOCK) PP_WAVES void psfm_chain_persist_kernel(P
     // ---- the tracks still active at the end (clear_active, trajectory.py:154-158): last valid time = n_flows ----
     const int lane = tid & (PSFM_WAVE - 1), wave = tid / PSFM_WAVE;
     {
+        const int nf = PA->n_flows;
         const bool alive = bf >= 0;
         const int slot = psfm_record_slot(&s_rec_cnt, alive);
-        if (alive) psfm_put_record(a, slot, psfm_key(a.n_flows, bf, s_gi[tid], a.shift_b, a.shift_d), L);
+        if (alive) psfm_put_record(slot, psfm_cold_key(nf, bf, s_gi[tid]), L);
         if (tid < PP_GUESTS && s_gbf[tid] >= 0) {
             const int gslot = atomicAdd(&s_rec_cnt, 1);
-            psfm_put_record(a, gslot, psfm_key(a.n_flows, s_gbf[tid], s_ggi[tid], a.shift_b, a.shift_d),
-                            a.cap_main + blockIdx.x * PP_GUESTS + tid);
+            psfm_put_record(gslot, psfm_cold_key(nf, s_gbf[tid], s_ggi[tid]),
+                            psfm_cold()->cap_main + PP_BID * PP_GUESTS + tid);
         }
     }
     // trajectory points written by this block (sizes the result without a second host sync)
@@ -707,7 +822,9 @@ __global__ __launch_bounds__(PP_BLOCK) PP_WAVES void psfm_chain_persist_kernel(P
             int tot = 0;
             for (int j = 0; j < PP_NW; ++j) tot += s_pts[j];
             const int c = s_rec_cnt;
-            a.seg_info[blockIdx.x] = make_int2(c < a.seg_cap ? c : a.seg_cap, tot);
+            const PsfmColdPtr cold = psfm_cold();
+            const int seg_cap = cold->seg_cap;
+            cold->seg_info[PP_BID] = make_int2(c < seg_cap ? c : seg_cap, tot);
         }
     }
 }
@@ -767,10 +884,12 @@ psfm_status psfm_launch_chain_persist(psfm_ctx* c, const PsfmTrackDims& d, const
                            c->shards.as<PsfmShard>(), (int)d.G, c->occupied.as<unsigned long long>(), n_maps64,
                            c->persist_bar.as<unsigned long long>(), n_bar64, c->handoff.as<unsigned long long>(), n_handoff);
     }
-    PsfmPersistArgs a;
-    a.flows = (const float2*)flows; a.occ = occ;
+    PsfmPersistKernarg ka;
+    PsfmPersistArgs& a = ka.hot;
+    PsfmPersistCold& k = ka.cold;
+    a.flows = (const float2*)flows; a.occ = const_cast<uint8_t*>(occ);
     a.occ_pitch = occ_pitch;
-    a.flows_b = (const float2*)flows_b; a.occ_w = const_cast<uint8_t*>(occ); a.thres = thres; a.t2 = psfm_sq_threshold(thres); a.fc = flows_b != nullptr;
+    a.flows_b = (const float2*)flows_b; a.t2 = psfm_sq_threshold(thres); a.fc = flows_b != nullptr;
     {
         static const int xcd_on = getenv("PSFM_FC_XCD") ? atoi(getenv("PSFM_FC_XCD")) : 1;
         const int64_t nch = ((int64_t)d.H * d.W + 1023) / 1024;
@@ -786,21 +905,20 @@ psfm_status psfm_launch_chain_persist(psfm_ctx* c, const PsfmTrackDims& d, const
     a.wdiv = psfm_fastdiv_make((unsigned)d.W);
     a.H = d.H; a.W = d.W; a.cw = d.cw; a.ch = d.ch; a.rcw = psfm_rcp_host(d.cw); a.rch = psfm_rcp_host(d.ch);
     a.ratio = d.ratio; a.GW = d.GW; a.GH = d.GH; a.G = (int)d.G;
-    a.dlog = c->log.as<float2>(); a.cap = (int)d.cap; a.cap_main = d.nblk * PP_BLOCK;
+    a.dlog = c->log.as<float2>(); a.cap = k.cap = (int)d.cap; k.cap_main = d.nblk * PP_BLOCK;
     a.maps = c->occupied.as<uint8_t>();
-    a.ctr = c->counters.as<PsfmCounters>();
-    a.shards = c->shards.as<PsfmShard>();
-    a.free_stack = c->free_stack.as<int>(); a.free_cap = d.free_cap; a.nsh = d.nsh;
+    k.ctr = c->counters.as<PsfmCounters>();
+    k.shards = c->shards.as<PsfmShard>();
+    k.free_stack = c->free_stack.as<int>(); k.free_cap = d.free_cap; k.nsh = d.nsh;
     a.handoff = c->handoff.as<unsigned long long>();
-    a.fin_keys = c->fin_keys.as<unsigned long long>(); a.fin_lanes = c->fin_lanes.as<int>();
-    a.seg_cap = d.seg_cap; a.spill_base = d.nblk * d.seg_cap; a.spill_cap = d.spill_cap;
-    a.seg_info = c->seg_info.as<int2>();
+    k.fin_keys = c->fin_keys.as<unsigned long long>(); k.fin_lanes = c->fin_lanes.as<int>();
+    k.seg_cap = d.seg_cap; k.spill_base = d.nblk * d.seg_cap; k.spill_cap = d.spill_cap;
+    k.seg_info = c->seg_info.as<int2>();
     a.bar = c->persist_bar.as<unsigned>();
-    a.survsh = a.bar + (2 * PSFM_NSHARD + 1) * 32;
-    a.n_flows = d.n_flows; a.shift_b = d.shift_b; a.shift_d = d.shift_d;
+    a.n_flows = d.n_flows; a.nblk = d.nblk; k.shift_b = d.shift_b; k.shift_d = d.shift_d;
     a.gwdiv = psfm_fastdiv_make((unsigned)d.GW); a.rdiv = psfm_fastdiv_make((unsigned)d.ratio);
-    a.spin_limit = 1 << 18;   // ~35 ms of polling before a block gives up (the per-frame path then reruns the sequence)
-    if (const char* e = getenv("PSFM_PERSIST_SPIN_LIMIT")) a.spin_limit = atoi(e);   // tests: 0 forces the hand-over
+    k.spin_limit = 1 << 18;   // ~35 ms of polling before a block gives up (the per-frame path then reruns the sequence)
+    if (const char* e = getenv("PSFM_PERSIST_SPIN_LIMIT")) k.spin_limit = atoi(e);   // tests: 0 forces the hand-over
     hipEvent_t e0 = nullptr, e1 = nullptr;
     c->prof.kernel_span(PSFM_PROF_CHAIN, &e0, &e1, true);
     const dim3 grid((unsigned)d.nblk), block(PP_BLOCK);
@@ -813,7 +931,7 @@ psfm_status psfm_launch_chain_persist(psfm_ctx* c, const PsfmTrackDims& d, const
     const void* fn = d.ratio == 1 ? (const void*)psfm_chain_persist_kernel<1> : d.ratio == 2 ? (const void*)psfm_chain_persist_kernel<2>
                    : d.ratio == 4 ? (const void*)psfm_chain_persist_kernel<4> : (const void*)psfm_chain_persist_kernel<0>;
     if (coop) {
-        void* kargs[] = {(void*)&a};
+        void* kargs[] = {(void*)&ka};
         if (e0) PSFM_HIP(hipEventRecord(e0, s));
         const hipError_t le = hipLaunchCooperativeKernel(fn, grid, block, kargs, 0, s);
         if (le != hipSuccess) {
@@ -825,10 +943,10 @@ psfm_status psfm_launch_chain_persist(psfm_ctx* c, const PsfmTrackDims& d, const
         return PSFM_OK;
     }
     switch (d.ratio) {
-        case 1: hipExtLaunchKernelGGL(psfm_chain_persist_kernel<1>, grid, block, 0, s, e0, e1, 0, a); break;
-        case 2: hipExtLaunchKernelGGL(psfm_chain_persist_kernel<2>, grid, block, 0, s, e0, e1, 0, a); break;
-        case 4: hipExtLaunchKernelGGL(psfm_chain_persist_kernel<4>, grid, block, 0, s, e0, e1, 0, a); break;
-        default: hipExtLaunchKernelGGL(psfm_chain_persist_kernel<0>, grid, block, 0, s, e0, e1, 0, a); break;
+        case 1: hipExtLaunchKernelGGL(psfm_chain_persist_kernel<1>, grid, block, 0, s, e0, e1, 0, ka); break;
+        case 2: hipExtLaunchKernelGGL(psfm_chain_persist_kernel<2>, grid, block, 0, s, e0, e1, 0, ka); break;
+        case 4: hipExtLaunchKernelGGL(psfm_chain_persist_kernel<4>, grid, block, 0, s, e0, e1, 0, ka); break;
+        default: hipExtLaunchKernelGGL(psfm_chain_persist_kernel<0>, grid, block, 0, s, e0, e1, 0, ka); break;
     }
     PSFM_HIP(hipGetLastError());
     return PSFM_OK;
