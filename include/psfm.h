@@ -20,6 +20,8 @@
  *                           id / min-length rule of main_connect_point_trajectories.py:56-60
  *   psfm_traj_augment       motion_seg/core/network/traj_oa_depth.py:72-114 augment_traj() (the classifier's 10-channel input)
  *   psfm_traj_encode        motion_seg/core/network/traj_oa_depth.py:25-60 pt_transformer.forward() (joint_encoder, eval mode)
+ *   psfm_traj_decode        motion_seg/core/network/oanet.py:13-206 OANBlock.forward() (traj_oa_depth.decoder, eval mode),
+ *                           traj_oa_depth.py:124 torch.sigmoid, main_motion_segmentation.py:80 `> 0.5`
  *   psfm_labels_*           motion_seg/main_motion_segmentation.py:89-129 (per-window predictions -> labelled track.npy)
  *
  * Conventions
@@ -41,6 +43,7 @@
 #ifndef PSFM_H_
 #define PSFM_H_
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -294,7 +297,7 @@ psfm_status psfm_traj_augment(psfm_ctx* ctx, const double* xy_norm, const double
 /* The motion classifier's trajectory transformer -- traj_oa_depth.joint_encoder(aug_trajs, masks) = pt_transformer.forward in eval
  * mode (motion_seg/core/network/traj_oa_depth.py:25-60) -- from exactly what psfm_traj_augment and psfm_window_sample wrote:
  * features [10][k][n_frames] f32, mask_absent (k,n_frames) f64 (padded where its .float() > 0.5).  out is the reference's [1,16,k]
- * fp32 tensor (what it hands to the OANet decoder as feat.unsqueeze(-1)); the decoder and the sigmoid stay with the caller.
+ * fp32 tensor (what it hands to the OANet decoder as feat.unsqueeze(-1)): psfm_traj_decode's input.
  * Per trajectory, tokens l = 0 .. n_frames-1, fp32, dropout off:
  *   x = relu(fc2(relu(input_fc1(f))))                                        two 1x1 convolutions, 10 -> 16 -> 16
  *   encoder layer x 2 (post-norm): h = LN1(h + SA(h)); h = LN2(h + linear2(relu(linear1(h)))); memory = encoder.norm(h)
@@ -324,6 +327,40 @@ psfm_status psfm_traj_augment(psfm_ctx* ctx, const double* xy_norm, const double
 int psfm_traj_encode_weight_count(void);
 psfm_status psfm_traj_encode(psfm_ctx* ctx, const float* features, const double* mask_absent, const float* weights, int64_t k,
                              int n_frames, float* out, void* stream);
+
+/* motion_seg/core/network/oanet.py:13-206: traj_oa_depth.decoder = OANBlock(net_channels 128, input_channel 16, depth 8, clusters 100)
+ * in eval mode on psfm_traj_encode's output, then torch.sigmoid (traj_oa_depth.py:124) and the `> 0.5` of
+ * main_motion_segmentation.py:80.  encoding [16][k] f32; logits, prob [k] f32 and pred [k] u8 (1 = dynamic: what
+ * psfm_labels_merge_window takes) may each be NULL.  The k trajectories are the points, B = 1, fp32 throughout:
+ *   x1_1 = l1_1(conv1(encoding)): conv 16 -> 128, then 4 x PointCN(128) = IN, BN, ReLU, conv, IN, BN, ReLU, conv, plus the input
+ *   down1: S = softmax over the k POINTS per cluster of conv 128 -> 100 of IN/BN/ReLU(x1_1); x_down [128][100] = x1_1 S^T (raw x1_1)
+ *   l2: 4 x OAFilter(128, 100): IN/BN/ReLU/conv 128 -> 128; across the clusters out + conv 100 -> 100 of BN/ReLU(out); IN/BN/ReLU/conv
+ *       128 -> 128, plus the input
+ *   up1: S = softmax over the 100 CLUSTERS per point of conv 128 -> 100 of IN/BN/ReLU(x1_1) (its own BN and conv); x_up = x2 S
+ *   l1_2: PointCN(256, 128) on cat(x1_1, x_up) (with its shot_cut conv 256 -> 128 of the raw input), 3 x PointCN(128)
+ *   logit = output conv 128 -> 1; prob = sigmoid(logit); pred = prob > 0.5 on the fp32 probability
+ * IN = InstanceNorm2d(eps 1e-3), no affine, no running statistics: the BIASED variance over the k points of this call, in eval mode
+ * too (so a row's result depends on all rows).  BN = BatchNorm2d in eval: running_mean / running_var (eps 1e-5) / weight / bias.
+ * Every product runs on the exact fp32 matrix instruction; channel statistics are f64 sums of the stored fp32 values, added across
+ * blocks in a fixed order: no floating-point atomics, two identical calls give identical bits.  Results agree with the module's f64
+ * evaluation as closely as the module's own fp32 run does (tests/golden/make_decoder_golden.py measures that error per case).
+ * weights: psfm_traj_decode_weight_count() = 529497 floats on the DEVICE: the decoder's 186 float tensors (521785 parameters, 7712
+ * running statistics) in the module's own state_dict order without the 30 num_batches_tracked, every tensor row-major as stored:
+ *   conv1.weight [128][16], .bias; down1, up1: conv.1 (BN: weight, bias, running_mean, running_var), conv.3.weight [100][128], .bias;
+ *   l1_1.{0..3}: conv.1 (BN), conv.3 [128][128], conv.5 (BN), conv.7 [128][128];
+ *   l1_2.0: shot_cut [128][256], conv.1 (BN 256), conv.3 [128][256], conv.5 (BN), conv.7; l1_2.{1..3} as l1_1;
+ *   l2.{0..3}: conv1.1 (BN), conv1.3 [128][128], conv2.0 (BN 100), conv2.2 [100][100], conv3.2 (BN), conv3.4 [128][128];
+ *   output.weight [128], .bias [1].  The kernels fold the BatchNorms: a checkpoint's tensors are passed as they are.
+ * workspace: psfm_traj_decode_workspace_bytes(k) bytes on the DEVICE, the caller's (about 2.6 KB per trajectory: four [128][k]
+ * activations, the [100][k] embedding, per-block partials); its contents before the call do not matter and are unspecified after.
+ * ASYNCHRONOUS: a fixed sequence of launches on `stream` whose number does not depend on the data, no allocation, no host
+ * synchronisation.  k = 0 is a no-op.  PSFM_ERR_ARG, nothing launched: k < 0; k == 1 (InstanceNorm2d needs more than one point: the
+ * reference raises); 128 k above 2^31 - 1 (the kernels' 32-bit indices); a NULL encoding, weights or workspace with k > 0;
+ * workspace_bytes too small (the message names the needed size; psfm_traj_decode_workspace_bytes returns 0 for a k it refuses). */
+int psfm_traj_decode_weight_count(void);
+size_t psfm_traj_decode_workspace_bytes(int64_t k);
+psfm_status psfm_traj_decode(psfm_ctx* ctx, const float* encoding, const float* weights, int64_t k, void* workspace,
+                             size_t workspace_bytes, float* logits, float* prob, uint8_t* pred, void* stream);
 
 /* sfm/matches_from_flow.py:51-118 (traj_to_matches) from the saved set that psfm_result_filter left in HBM -- the
  * reference's per-trajectory Python loops as index arithmetic on the device (no track.npy round trip):
