@@ -165,6 +165,52 @@ __device__ __forceinline__ float psfm_sample_mask(const uint8_t* __restrict__ ma
     return psfm_sample_mask(map, psfm_tap_idx(H, W, t), t);
 }
 
+// ---- tap PAIRS: the west and the east tap of a row are neighbours in memory (two pixels of the (H,W,2) flow are 16 contiguous
+// bytes), so a bilinear flow sample needs two addresses, not four.  One branch-free path for interior and border: the pair of a
+// row starts at column xb = min(max(x0, 0), W - 2) (W >= 2: psfm_frame_ok), `lo` is pixel xb and `hi` pixel xb + 1.  The west tap is
+// `lo` unless x0 > xb (only x0 = W-1: the map's last column is the pair's `hi`), the east tap is `hi` unless x0 < xb (only x0 = -1:
+// the map's first column is the pair's `lo`).  Zeros padding is the same select as in the four-tap form, AFTER the pick: an outside
+// tap is exactly 0.0f, and neither the pair's other pixel nor a clamped duplicate reaches the blend.  Same bytes, same bits, half
+// the vector-memory instructions -- for eight more selects per sample: it pays where the loads queue (the persistent loop's fused
+// flow_check slices), not in the chain step (profiles/EXPERIMENTS.md section 14). ----
+struct __attribute__((packed, aligned(8), may_alias)) PsfmFlowPair { float lx, ly, hx, hy; };   // 8-byte aligned: ONE global_load_dwordx4
+
+__device__ __forceinline__ PsfmFlowPair psfm_ld_flow_pair(const float2* __restrict__ map, unsigned byte_off)
+{
+    return *(const PsfmFlowPair*)((const char*)map + byte_off);
+}
+
+struct PsfmPairIdx {
+    int n, s;                    // element offsets of the north / south row's pair (pixel (row, xb); rows clamped into the map)
+    bool whi, elo;               // the west tap is the pair's `hi` / the east tap is its `lo`
+    bool inw, ine, isw, ise;     // tap inside the map?
+};
+__device__ __forceinline__ PsfmPairIdx psfm_pair_idx(int H, int W, const PsfmTaps& t)
+{
+    const int x0 = t.x0, y0 = t.y0, x1 = t.x0 + 1, y1 = t.y0 + 1;
+    const bool xw = (x0 >= 0) & (x0 < W), xe = (x1 >= 0) & (x1 < W);
+    const bool yn = (y0 >= 0) & (y0 < H), ys = (y1 >= 0) & (y1 < H);
+    const int xb = min(max(x0, 0), W - 2);
+    PsfmPairIdx k;
+    k.n = min(max(y0, 0), H - 1) * W + xb;
+    k.s = min(max(y1, 0), H - 1) * W + xb;
+    k.whi = x0 > xb; k.elo = x0 < xb;
+    k.inw = xw & yn; k.ine = xe & yn; k.isw = xw & ys; k.ise = xe & ys;
+    return k;
+}
+// psfm_sample_flow(map, H, W, t) with two 16-byte loads
+__device__ __forceinline__ float2 psfm_sample_flow_pairs(const float2* __restrict__ map, int H, int W, const PsfmTaps& t)
+{
+    const PsfmPairIdx k = psfm_pair_idx(H, W, t);
+    const PsfmFlowPair pn = psfm_ld_flow_pair(map, (unsigned)k.n * 8u), ps = psfm_ld_flow_pair(map, (unsigned)k.s * 8u);
+    const float z = 0.0f;
+    const float nwx = k.inw ? (k.whi ? pn.hx : pn.lx) : z, nwy = k.inw ? (k.whi ? pn.hy : pn.ly) : z;
+    const float nex = k.ine ? (k.elo ? pn.lx : pn.hx) : z, ney = k.ine ? (k.elo ? pn.ly : pn.hy) : z;
+    const float swx = k.isw ? (k.whi ? ps.hx : ps.lx) : z, swy = k.isw ? (k.whi ? ps.hy : ps.ly) : z;
+    const float sex = k.ise ? (k.elo ? ps.lx : ps.hx) : z, sey = k.ise ? (k.elo ? ps.ly : ps.hy) : z;
+    return make_float2(psfm_blend(nwx, nex, swx, sex, t), psfm_blend(nwy, ney, swy, sey, t));
+}
+
 // One-channel f32 sample (API parity for psfm_grid_sample with C == 1).
 __device__ __forceinline__ float psfm_sample_f32(const float* __restrict__ map, int H, int W, const PsfmTaps& t)
 {

@@ -48,8 +48,12 @@
                          // 1080p sequence end to end: window 4 -> 2.80 ms, 3 -> 2.84, 8 -> 2.96, unbounded -> 3.19 (front-loads the
                          // memory system), slices also behind the barrier -> 3.12, always one slice per frame -> 2.86
 #endif
-#ifndef PP_FC_FAST
-#define PP_FC_FAST 0     // fused flow_check: wave-uniform "all taps interior" form (16-byte tap pairs, no padding selects)
+#ifndef PP_FC_PAIRS
+#define PP_FC_PAIRS 1    // fused flow_check: the two taps of a row of B as ONE 16-byte load (psfm_device.h, tap pairs): 8 instead of 16 tap loads per
+                         // thread and chunk, same bytes and bits.  Measured: 18.2 -> 17.7 us per fused step (0: four 8-byte loads; measurement
+                         // builds).  The same pairing in the chain step measured slower and is not used.  Why -- fewer wave-instructions in a
+                         // memory pipe that is busy while a map streams, against eight more selects per sample -- is a reading of the timings,
+                         // not of counters: profiles/EXPERIMENTS.md section 14
 #endif
 #define PP_GUESTS 32   // extra lanes per block whose state lives in LDS (stepped as phase-2 entries)
 #ifndef PP_WHATIF
@@ -310,19 +314,8 @@ __device__ __forceinline__ void psfm_fc_slice(int f, int tid)
         for (int k = 0; k < 4; ++k) {
             const int p = p0 + k * 256;
             if (p >= P) break;
-            uint8_t o;
-#if PP_FC_FAST
-            {   // wave-uniform short cut: every lane's taps inside the map (all but the border waves)
-                const float X = __fadd_rn((float)x, fv[k].x), Y = __fadd_rn((float)y, fv[k].y);
-                const PsfmTaps t = psfm_taps_t<true>(X, Y, q.cw, q.ch, q.rcw, q.rch, q.H, q.W);
-                const bool interior = (t.x0 >= 0) & (t.x0 + 1 < q.W) & (t.y0 >= 0) & (t.y0 + 1 < q.H);
-                if (__builtin_amdgcn_ballot_w64(!interior) == 0ull) o = psfm_flow_check_px_interior(B, X, Y, fv[k], t, q);
-                else { float e; int xb = x, yb = y; asm volatile("" : "+v"(xb), "+v"(yb)); o = psfm_flow_check_px<false>(B, xb, yb, fv[k], q, &e); }
-            }
-#else
             float e;
-            o = psfm_flow_check_px<false>(B, x, y, fv[k], q, &e);
-#endif
+            const uint8_t o = psfm_flow_check_px<false, PP_FC_PAIRS != 0>(B, x, y, fv[k], q, &e);
             psfm_coh_st(O + p, o);
             x += 256;
             while (x >= W) { x -= W; ++y; }
