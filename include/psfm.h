@@ -23,6 +23,8 @@
  *   psfm_traj_decode        motion_seg/core/network/oanet.py:13-206 OANBlock.forward() (traj_oa_depth.decoder, eval mode),
  *                           traj_oa_depth.py:124 torch.sigmoid, main_motion_segmentation.py:80 `> 0.5`
  *   psfm_labels_*           motion_seg/main_motion_segmentation.py:89-129 (per-window predictions -> labelled track.npy)
+ *   psfm_traj_eval_counts   motion_seg/eval_traj_iou.py:53-115 per_img_traj_metrics() (labelled points against ground-truth masks)
+ *   psfm_traj_vote_labels   scripts/prepare_flyingthings3d.py:89-108 find_traj_label() (a trajectory's training label)
  *
  * Conventions
  *   - plain C, no C++/torch types.  Every data pointer is a DEVICE pointer
@@ -424,6 +426,42 @@ psfm_status psfm_labels_copy(psfm_ctx* ctx, int32_t* ids_out, int64_t* off_out, 
                              uint8_t* labels_out, void* stream);
 psfm_status psfm_labels_to_matches(psfm_ctx* ctx, int n_img, int sample_k, int remove_dynamic, int64_t* n_kp_host,
                                    int64_t* n_matches_host, int64_t* n_pairs_host, void* stream);
+
+/* Trajectories against ground-truth masks (csrc/psfm_ground_truth.hip; the two per-element rules are csrc/psfm_ground_truth.h).
+ * psfm_traj_eval_counts     motion_seg/eval_traj_iou.py:79-115 (per_img_traj_metrics) reduced to what its four metrics are functions
+ *                           of: per frame, the counts tp, fp, fn, tn over the labelled points of that frame.  A point (x, y) f64 is
+ *                           rounded to fp32 and sampled by the sampler of psfm_grid_sample (:53-65: true division by (size-1)/2,
+ *                           bilinear, zeros padding, align_corners) from its frame's mask; gt = sample > 0.5f, pred = label != 0
+ *                           (:70).  The mask is a u8 map seen through a 256-entry fp32 table: tap value = table_host[byte], a tap
+ *                           outside the image = 0.  (The reference's mask is 1.0 - png[:,:,0] / 255.0 in f64 (:49) cast to fp32
+ *                           (:107), i.e. table[b] = (float)(1.0 - b / 255.0); a caller with 0/1 masks passes another table.)
+ *                             frame_ids (n_points) i32, xy (n_points,2) f64, labels (n_points) u8: DEVICE arrays, e.g. the CSR of
+ *                               psfm_labels_device.  All three NULL = the labelled set that psfm_labels_finish left in the context
+ *                               (n_points is then ignored; no such set: PSFM_ERR_ARG).  One or two NULL: PSFM_ERR_ARG.
+ *                             masks_u8 (n_frames,h,w) u8 DEVICE; table_host 256 fp32 on the HOST (read before the call returns)
+ *                             counts_out (n_frames,4) i64 DEVICE: tp, fp, fn, tn of frame f over the points with frame id f.  A
+ *                               point whose frame id is outside [0, n_frames) is ignored (nothing is read for it).
+ *                           ASYNCHRONOUS: a memset and one launch on `stream`, no allocation, no host synchronisation.  n_points = 0
+ *                           (with non-NULL arrays) gives zeros.  The counts are integers accumulated with integer atomics: two calls
+ *                           on the same input give identical counts.  PSFM_ERR_ARG, nothing launched: n_points < 0, n_frames < 1,
+ *                           h or w < 2 (the sampler divides by (w-1)/2), 8*h*w >= 2^32 (the 32-bit byte offsets of every entry
+ *                           point that takes h, w), a NULL masks_u8 / table_host / counts_out.
+ * psfm_traj_vote_labels     scripts/prepare_flyingthings3d.py:89-108 (find_traj_label) from exactly what psfm_window_sample wrote
+ *                           for a window that covers the sequence: xy (k,n_frames,2) f64 raw positions, mask_absent (k,n_frames) f64
+ *                           (nonzero = padded), plus gts_u8 (n_frames,h,w) u8; labels_out (k) u8.  Per row: over the present
+ *                           columns j, label_num += gts[j][rint(y)][rint(x)] -- rint rounds half to even like Python's round() on a
+ *                           numpy.float64; the sum is an integer that cannot wrap (NumPy 1.21's behaviour; a u8 sum would wrap at
+ *                           256) -- and label = label_num > total_num / 2 with integer division, total_num = the number of present
+ *                           columns; a row without one gets 0.  Deviation: a present point whose pixel is outside [0,h) x [0,w), or
+ *                           that is not finite, is never read; the call then returns PSFM_ERR_ARG and labels_out is unspecified
+ *                           (every access stayed in bounds).  The reference wraps a negative index and raises on one >= h.
+ *                           Synchronises `stream`.  k = 0 is a no-op.  PSFM_ERR_ARG, nothing launched: k < 0, n_frames < 1, h or
+ *                           w < 1, h*w above 2^31 - 1, a NULL pointer with k > 0. */
+psfm_status psfm_traj_eval_counts(psfm_ctx* ctx, const int32_t* frame_ids, const double* xy, const uint8_t* labels, int64_t n_points,
+                                  const uint8_t* masks_u8, const float* table_host, int n_frames, int h, int w, int64_t* counts_out,
+                                  void* stream);
+psfm_status psfm_traj_vote_labels(psfm_ctx* ctx, const double* xy, const double* mask_absent, const uint8_t* gts_u8, int64_t k,
+                                  int n_frames, int h, int w, uint8_t* labels_out, void* stream);
 
 /* ONE sequence over several processes / GPUs, exactly (psfm_dist.connect_sharded drives these).
  * The tracks are split by the row band of the stride-r grid they are born on: this process owns the births on grid points

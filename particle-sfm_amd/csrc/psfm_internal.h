@@ -214,6 +214,7 @@ struct psfm_ctx {
     PsfmBuf lb_ws;                       // finish: counts, sort halves
     PsfmBuf lb_ids, lb_off, lb_frames, lb_xy, lb_labels;   // the labelled set, CSR in order of first appearance
     int64_t lb_n_traj = 0, lb_n_points = 0;
+    PsfmBuf gt_flag;                     // psfm_traj_vote_labels (psfm_ground_truth.hip): a present point outside the image
     hipStream_t side_stream = nullptr;   // flow_check of psfm_connect runs here, ahead of the frame loop
     hipStream_t copy_stream = nullptr;   // psfm_load_flo_stack: H2D copies out of the pinned ring
     hipStream_t copy_stream2 = nullptr;  // ... every second slot's copies (two SDMA engines; PSFM_FLO_COPY_STREAMS=1: one)

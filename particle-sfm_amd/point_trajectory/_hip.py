@@ -28,6 +28,7 @@ EXPORTS = [
     "psfm_labels_begin", "psfm_labels_merge_window", "psfm_labels_finish", "psfm_labels_device", "psfm_labels_copy", "psfm_labels_to_matches",
     "psfm_traj_augment", "psfm_traj_encode_weight_count", "psfm_traj_encode",
     "psfm_traj_decode_weight_count", "psfm_traj_decode_workspace_bytes", "psfm_traj_decode",
+    "psfm_traj_eval_counts", "psfm_traj_vote_labels",
 ]
 
 
@@ -109,6 +110,8 @@ def lib():
     L.psfm_traj_decode_weight_count.argtypes = []
     L.psfm_traj_decode_workspace_bytes.argtypes = [i64]
     L.psfm_traj_decode.argtypes = [vp, vp, vp, i64, vp, ctypes.c_size_t, vp, vp, vp, vp]
+    L.psfm_traj_eval_counts.argtypes = [vp, vp, vp, vp, i64, vp, vp, i32, i32, i32, vp, vp]
+    L.psfm_traj_vote_labels.argtypes = [vp, vp, vp, vp, i64, i32, i32, i32, vp, vp]
     L.psfm_traj_to_matches.argtypes = [vp, i32, i32, vp, ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(i64), vp]
     L.psfm_matches_copy.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
     L.psfm_labels_begin.argtypes = [vp, vp]
