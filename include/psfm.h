@@ -415,7 +415,16 @@ psfm_status psfm_matches_copy(psfm_ctx* ctx, int64_t* kp_off_host, double* kp_xy
  *                           pipeline, same context tables -- read them with psfm_matches_copy), with the trajectories in the
  *                           set's order (the dict order :67 iterates in), a point's frame from frame_ids, and the kept points =
  *                           labels == 0 when remove_dynamic != 0 (:71-74), all points otherwise.  A frame outside [0, n_img) is
- *                           PSFM_ERR_ARG.  Synchronises `stream`. */
+ *                           PSFM_ERR_ARG.  Synchronises `stream`.
+ * psfm_labels_set           a labelled set from elsewhere (a labelled track.npy, another classifier): the caller's CSR -- the five
+ *                           arrays of psfm_labels_finish, HOST or DEVICE (the direction follows from the pointer) -- is copied into
+ *                           the context and becomes its labelled set, exactly as if psfm_labels_finish had built it; a merge in
+ *                           progress ends (psfm_labels_begin starts a new one).  The trajectories keep the given order; a
+ *                           trajectory's frames may come in any order and have gaps.  PSFM_ERR_ARG: negative sizes, a NULL array
+ *                           that is not empty, or an off that does not run from 0 to n_points without stepping back (checked on
+ *                           the device: the context then holds no labelled set).  Synchronises `stream`. */
+psfm_status psfm_labels_set(psfm_ctx* ctx, int64_t n_traj, int64_t n_points, const int32_t* ids, const int64_t* off,
+                            const int32_t* frame_ids, const double* xy, const uint8_t* labels, void* stream);
 psfm_status psfm_labels_begin(psfm_ctx* ctx, void* stream);
 psfm_status psfm_labels_merge_window(psfm_ctx* ctx, int frame0, int n_frames, const int32_t* ids_dev, const uint8_t* pred_dev,
                                      int64_t k, void* stream);
@@ -426,6 +435,44 @@ psfm_status psfm_labels_copy(psfm_ctx* ctx, int32_t* ids_out, int64_t* off_out, 
                              uint8_t* labels_out, void* stream);
 psfm_status psfm_labels_to_matches(psfm_ctx* ctx, int n_img, int sample_k, int remove_dynamic, int64_t* n_kp_host,
                                    int64_t* n_matches_host, int64_t* n_pairs_host, void* stream);
+
+/* sfm/import_feature_matches.py:76-104 (import_keypoints_matches) writing through sfm/colmap_utils/database.py:181-225: the match
+ * tables that the last psfm_traj_to_matches / psfm_labels_to_matches left in the context become the blobs of the COLMAP database's
+ * keypoints, matches and two_view_geometries rows (csrc/psfm_database.hip; the per-element rules are csrc/psfm_database.h).
+ * psfm_matches_to_database   db_id_host, db_pos_host (n_img) i32 on the HOST, indexed by image = frame index: the image's COLMAP
+ *                            image_id, and its position in the order the reference iterates its image_ids mapping in (the order of
+ *                            the SELECT that built it: neither name order nor id order).
+ *                              keypoints  float32(xy + 0.5): the add in f64, one rounding to f32 (:82-84, database.py:185); same
+ *                                         kp_off as the match tables
+ *                              pairs      directed pair (s, t) is written unless the reverse pair (t, s) is in the table and
+ *                                         pos[t] < pos[s] -- what the reference's `matched` set amounts to (:88-99); a self pair is
+ *                                         written.  With more than sample_k kept points in a trajectory the two directions hold
+ *                                         different matches: the reference drops data here, and so does this.
+ *                              rows       pair_id = min(id_s, id_t) * (2^31 - 1) + max(id_s, id_t) i64; rows u32, the two columns
+ *                                         swapped when id_s > id_t (database.py:196-207); the kept pairs in ascending pair_key
+ *                                         order, their rows contiguous and in the match table's order
+ *                            Returns the number of kept pairs and of their rows; synchronises `stream`.  Integers in a fixed order:
+ *                            two calls on the same tables give identical bytes.  PSFM_ERR_ARG (the context stays usable, earlier
+ *                            database tables are kept): no match tables in the context; n_img differs from the one they were built
+ *                            with; an id outside [1, 2^31 - 2]; an id given twice; db_pos not a permutation of 0..n_img-1; a NULL
+ *                            argument.
+ * psfm_database_copy         copies the tables into caller-provided buffers, HOST or DEVICE (the direction follows from the pointer),
+ *                            any may be NULL; synchronises `stream`:
+ *                              kp_f32 (n_kp,2) f32 -- keypoints of image i = rows kp_off[i] .. kp_off[i+1] (psfm_matches_copy)
+ *                              pair_id (n_pairs_kept) i64;  pair_key (n_pairs_kept) i64 = src * n_img + tgt of the kept pairs,
+ *                              ascending;  pair_off (n_pairs_kept+1) i64 into rows;  rows (n_rows_kept,2) u32
+ *                            The database tables are a copy of their own: they stay valid when the match tables are rebuilt.
+ *                            PSFM_ERR_ARG before the first successful psfm_matches_to_database.
+ * psfm_database_chunk_rows   output rows per block of the row compaction (the tests place pair boundaries around it).
+ * psfm_database_compact_again  for measurement: the row-compaction launch of the last psfm_matches_to_database once more, same
+ *                            input, same output bytes.  ASYNCHRONOUS: one launch on `stream`.  PSFM_ERR_ARG when the match tables
+ *                            were rebuilt since (or no database tables exist). */
+psfm_status psfm_matches_to_database(psfm_ctx* ctx, int n_img, const int32_t* db_id_host, const int32_t* db_pos_host,
+                                     int64_t* n_pairs_kept_host, int64_t* n_rows_kept_host, void* stream);
+psfm_status psfm_database_copy(psfm_ctx* ctx, float* kp_f32, int64_t* pair_id, int64_t* pair_key, int64_t* pair_off, uint32_t* rows,
+                               void* stream);
+int psfm_database_chunk_rows(void);
+psfm_status psfm_database_compact_again(psfm_ctx* ctx, void* stream);
 
 /* Trajectories against ground-truth masks (csrc/psfm_ground_truth.hip; the two per-element rules are csrc/psfm_ground_truth.h).
  * psfm_traj_eval_counts     motion_seg/eval_traj_iou.py:79-115 (per_img_traj_metrics) reduced to what its four metrics are functions

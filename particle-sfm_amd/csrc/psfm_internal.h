@@ -214,6 +214,12 @@ struct psfm_ctx {
     PsfmBuf lb_ws;                       // finish: counts, sort halves
     PsfmBuf lb_ids, lb_off, lb_frames, lb_xy, lb_labels;   // the labelled set, CSR in order of first appearance
     int64_t lb_n_traj = 0, lb_n_points = 0;
+    // psfm_matches_to_database (psfm_database.hip): the COLMAP database tables, a copy of their own beside the match tables
+    PsfmBuf db_kp, db_pairs, db_rows, db_ws;   // kp f32 (n_kp,2); pair_id | pair_key | pair_off, db_cap entries apart; rows u32; workspace
+    int64_t db_n_kp = 0, db_n_pairs = 0, db_n_rows = 0, db_cap = 0;
+    int db_n_img = 0;
+    bool db_valid = false;
+    bool db_src_live = false;            // the match tables are still the ones the database tables were built from (psfm_database_compact_again)
     PsfmBuf gt_flag;                     // psfm_traj_vote_labels (psfm_ground_truth.hip): a present point outside the image
     hipStream_t side_stream = nullptr;   // flow_check of psfm_connect runs here, ahead of the frame loop
     hipStream_t copy_stream = nullptr;   // psfm_load_flo_stack: H2D copies out of the pinned ring

@@ -266,6 +266,59 @@ extern "C" psfm_status psfm_labels_finish(psfm_ctx* c, int64_t* n_traj_host, int
     return PSFM_OK;
 }
 
+// off (k+1) must run from 0 to n_points without stepping back: the match-table kernels index by it
+__global__ __launch_bounds__(PL_BLOCK) void pl_check_off_kernel(const int64_t* __restrict__ off, int64_t k, int64_t n_points, int* __restrict__ flag)
+{
+    const int64_t t = (int64_t)blockIdx.x * PL_BLOCK + threadIdx.x;
+    if (t > k) return;
+    const int64_t a = off[t];
+    const bool bad = t == 0 ? a != 0 : (a < off[t - 1] || (t == k && a != n_points));
+    if (bad) *flag = 1;
+}
+
+// A labelled set from elsewhere (a labelled track.npy, labels of another classifier): the caller's CSR becomes the context's
+// labelled set, as if psfm_labels_finish had built it.
+extern "C" psfm_status psfm_labels_set(psfm_ctx* c, int64_t n_traj, int64_t n_points, const int32_t* ids, const int64_t* off,
+                                       const int32_t* frame_ids, const double* xy, const uint8_t* labels, void* stream)
+{
+    if (!c) { psfm_set_error("ctx is NULL"); return PSFM_ERR_ARG; }
+    if (n_traj < 0 || n_points < 0 || n_traj >= 0x7fffffffll || !off || (n_traj > 0 && !ids) || (n_points > 0 && (!frame_ids || !xy || !labels))) {
+        psfm_set_error("psfm_labels_set: bad argument (n_traj=%lld n_points=%lld)", (long long)n_traj, (long long)n_points);
+        return PSFM_ERR_ARG;
+    }
+    PSFM_HIP(hipSetDevice(c->device));
+    PsfmGate gate(c->device, 0);
+    hipStream_t s = (hipStream_t)stream;
+    psfm_status st;
+    c->lb_active = c->lb_finished = false;         // (a merge in progress ends here)
+    c->lb_n_traj = c->lb_n_points = 0;
+    if ((st = c->lb_ids.ensure(4 * (size_t)(n_traj > 0 ? n_traj : 1))) != PSFM_OK) return st;
+    if ((st = c->lb_off.ensure(8 * (size_t)(n_traj + 1))) != PSFM_OK) return st;
+    if ((st = c->lb_frames.ensure(4 * (size_t)(n_points > 0 ? n_points : 1))) != PSFM_OK) return st;
+    if ((st = c->lb_xy.ensure(16 * (size_t)(n_points > 0 ? n_points : 1))) != PSFM_OK) return st;
+    if ((st = c->lb_labels.ensure((size_t)(n_points > 0 ? n_points : 1))) != PSFM_OK) return st;
+    if ((st = c->lb_flag.ensure(256)) != PSFM_OK) return st;
+    if (n_traj > 0) PSFM_HIP(hipMemcpyAsync(c->lb_ids.p, ids, 4 * (size_t)n_traj, hipMemcpyDefault, s));
+    PSFM_HIP(hipMemcpyAsync(c->lb_off.p, off, 8 * (size_t)(n_traj + 1), hipMemcpyDefault, s));
+    if (n_points > 0) {
+        PSFM_HIP(hipMemcpyAsync(c->lb_frames.p, frame_ids, 4 * (size_t)n_points, hipMemcpyDefault, s));
+        PSFM_HIP(hipMemcpyAsync(c->lb_xy.p, xy, 16 * (size_t)n_points, hipMemcpyDefault, s));
+        PSFM_HIP(hipMemcpyAsync(c->lb_labels.p, labels, (size_t)n_points, hipMemcpyDefault, s));
+    }
+    int* flag = c->lb_flag.as<int>() + 1;           // (word 0 is the merge's unknown-id flag)
+    int64_t* h = (int64_t*)((char*)c->host_pinned + 256);
+    h[0] = 0;
+    PSFM_HIP(hipMemsetAsync(flag, 0, 4, s));
+    hipLaunchKernelGGL(pl_check_off_kernel, dim3(pl_grid(n_traj + 1)), dim3(PL_BLOCK), 0, s, (const int64_t*)c->lb_off.as<int64_t>(), n_traj, n_points, flag);
+    PSFM_HIP(hipGetLastError());
+    PSFM_HIP(hipMemcpyAsync(h, flag, 4, hipMemcpyDeviceToHost, s));
+    PSFM_HIP(hipStreamSynchronize(s));
+    if ((int)(h[0] & 0xffffffff) != 0) { psfm_set_error("psfm_labels_set: off does not run from 0 to n_points=%lld in ascending order", (long long)n_points); return PSFM_ERR_ARG; }
+    c->lb_n_traj = n_traj; c->lb_n_points = n_points;
+    c->lb_finished = true;
+    return PSFM_OK;
+}
+
 // the labelled set is a copy of its own: it stays readable after the saved set it was built from is gone
 static psfm_status pl_finished(psfm_ctx* c, const char* who)
 {

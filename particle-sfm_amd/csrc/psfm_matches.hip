@@ -196,6 +196,7 @@ psfm_status psfm_match_tables(psfm_ctx* c, const PsfmMatchSrc& src, int n_img, i
     PsfmGate gate(c->device, 0);
     *n_kp_host = *n_matches_host = *n_pairs_host = 0;
     c->mt_n_kp = c->mt_n_m = c->mt_n_pairs = 0; c->mt_n_img = n_img;
+    c->db_src_live = false;                                  // (psfm_database.hip: the database tables themselves stay valid)
     psfm_status st;
     if ((st = c->mt_kp_off.ensure(8 * (size_t)(n_img + 1))) != PSFM_OK) return st;
     PSFM_HIP(hipMemsetAsync(c->mt_kp_off.p, 0, 8 * (size_t)(n_img + 1), s));

@@ -29,6 +29,8 @@ EXPORTS = [
     "psfm_traj_augment", "psfm_traj_encode_weight_count", "psfm_traj_encode",
     "psfm_traj_decode_weight_count", "psfm_traj_decode_workspace_bytes", "psfm_traj_decode",
     "psfm_traj_eval_counts", "psfm_traj_vote_labels",
+    "psfm_labels_set", "psfm_matches_to_database", "psfm_database_copy", "psfm_database_chunk_rows",
+    "psfm_database_compact_again",
 ]
 
 
@@ -120,6 +122,11 @@ def lib():
     L.psfm_labels_device.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp)]
     L.psfm_labels_copy.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.psfm_labels_to_matches.argtypes = [vp, i32, i32, i32, ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(i64), vp]
+    L.psfm_labels_set.argtypes = [vp, i64, i64, vp, vp, vp, vp, vp, vp]
+    L.psfm_matches_to_database.argtypes = [vp, i32, vp, vp, ctypes.POINTER(i64), ctypes.POINTER(i64), vp]
+    L.psfm_database_copy.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.psfm_database_chunk_rows.argtypes = []
+    L.psfm_database_compact_again.argtypes = [vp, vp]
     L.psfm_shard_begin.argtypes = [vp, i32, i32, i32, i32, i64, i64, i32, vp, i64, vp]
     L.psfm_shard_step.argtypes = [vp, vp, vp, i32, vp]
     L.psfm_shard_solve_export.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp]
