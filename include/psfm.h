@@ -474,6 +474,57 @@ psfm_status psfm_database_copy(psfm_ctx* ctx, float* kp_f32, int64_t* pair_id, i
 int psfm_database_chunk_rows(void);
 psfm_status psfm_database_compact_again(psfm_ctx* ctx, void* stream);
 
+/* sfm/convert.py:43-104 (save_depth_pose): the sparse depth maps of the registered images of a COLMAP model (csrc/psfm_sparse_depth.hip;
+ * the per-element rules are csrc/psfm_sparse_depth.h).
+ * psfm_sparse_depth          obs_xy (n_obs,2) f64, obs_id (n_obs) i64: the concatenated point lists of the model's images (xys,
+ *                            point3D_ids), DEVICE.  img_desc_host: n_img descriptors on the HOST, 64 bytes each:
+ *                              i64 obs_begin, obs_end   the image's observations, in list order
+ *                              f64 r20, r21, r22, t2    row 2 of R = qvec2rotmat(qvec) (read_write_model.py:459-469, evaluated by the
+ *                                                       caller so that R is the reference's) and tvec[2]
+ *                              i32 w, h                 the image's camera
+ *                              i64 out_off              first element of its (h, w) map in depth_out: the maps of a call follow each
+ *                                                       other without gaps, the first at 0 -- cameras of different sizes share a call
+ *                            pt_id_sorted (n_pts) i64 ascending, pt_row (n_pts) i32 = the row of pt_xyz that holds that id (equal
+ *                            ids in file order: the last one is used, as a dict built in file order would), pt_xyz (n_pts,3) f64:
+ *                            DEVICE.  depth_out: DEVICE, sum of h * w f64.
+ *                              pixel   clip(int32(round-half-even(x)), 0, w - 1), y with h (:88-90), from xys, not from the projection
+ *                              depth   ((r20 X + r21 Y) + r22 Z) + t2, each operation rounded once (:86-87 is this sum in BLAS's
+ *                                      order: within 4 * 2^-53 * (|r20 X| + |r21 Y| + |r22 Z| + |t2|) of it)
+ *                              id -1   skipped (:77); a pixel that several observations round into holds the LAST one's depth (:91),
+ *                                      found as an integer maximum of list positions: no floating-point atomics, identical bytes
+ *                                      from identical calls; a pixel nobody rounds into holds 0.0
+ *                            Synchronises `stream`.  PSFM_ERR_ARG (the context stays usable; depth_out is then unspecified): an
+ *                            observation whose id names no point -- *missing_id_host (may be NULL) = the smallest such id, -1
+ *                            otherwise; a coordinate of a counted observation that is not finite or whose rounded value int32 does
+ *                            not hold (|v| >= 2^31, or rint(v) = 2^31: the reference's cast is platform-defined there); a pt_row
+ *                            outside [0, n_pts); descriptors that leave [0, n_obs), overlap or leave gaps in depth_out, w or h < 1,
+ *                            2^32 - 1 or more observations in one image; NaN in a pose; n_pts >= 2^31.  The winner map (u32 per
+ *                            pixel) and the rows found for the observations live in the context's workspace.
+ * psfm_sparse_depth_sort_ids pt_id (n_pts) i64 DEVICE, every id in [0, 2^32) -> pt_id_sorted, pt_row through the record sort of the
+ *                            finalize (stable).  PSFM_ERR_ARG on an id outside that range: sort those on the host (stable argsort).
+ * psfm_ctx_set_sparse_depth  budget_bytes: what callers that split a model into several psfm_sparse_depth calls (psfm_sfm.convert)
+ *                            let the maps + winner maps of one call take, 12 bytes per pixel; one image always goes through; 0 = no
+ *                            limit; default 2^30.  timing != 0: events around the zero fill, the winner pass and the store pass of
+ *                            every call, read by psfm_sparse_depth_last_ms (ms3[0..2], milliseconds).
+ * psfm_colmap_points3d_count / _scan   HOST code, no GPU is touched: the walk over a points3D.bin image in memory
+ *                            (read_write_model.py:336-363): u64 count, per point 43 bytes (u64 id, 3 f64 xyz, 3 u8 rgb, f64 error), a
+ *                            u64 track length L and 8 L bytes.  count -> *n; scan -> ids_out (n) u64, xyz_out (n,3) f64, err_out (n)
+ *                            f64, track_len_out (n) u64, any may be NULL.  Every read is checked against nbytes first.  The buffer
+ *                            must hold exactly the announced records: a buffer cut at ANY byte, record boundaries included, and one
+ *                            with trailing bytes are PSFM_ERR_ARG with the record index in psfm_last_error(); scan then writes
+ *                            nothing. */
+psfm_status psfm_sparse_depth(psfm_ctx* ctx, const double* obs_xy, const int64_t* obs_id, int64_t n_obs, const void* img_desc_host,
+                              int n_img, const int64_t* pt_id_sorted, const int32_t* pt_row, const double* pt_xyz, int64_t n_pts,
+                              double* depth_out, int64_t* missing_id_host, void* stream);
+psfm_status psfm_sparse_depth_sort_ids(psfm_ctx* ctx, const int64_t* pt_id, int64_t n_pts, int64_t* pt_id_sorted, int32_t* pt_row,
+                                       void* stream);
+psfm_status psfm_ctx_set_sparse_depth(psfm_ctx* ctx, int64_t budget_bytes, int timing);
+psfm_status psfm_ctx_get_sparse_depth_budget(psfm_ctx* ctx, int64_t* budget_bytes);
+psfm_status psfm_sparse_depth_last_ms(psfm_ctx* ctx, double* ms3);
+psfm_status psfm_colmap_points3d_count(const void* buf, uint64_t nbytes, uint64_t* n);
+psfm_status psfm_colmap_points3d_scan(const void* buf, uint64_t nbytes, uint64_t* ids_out, double* xyz_out, double* err_out,
+                                      uint64_t* track_len_out);
+
 /* Trajectories against ground-truth masks (csrc/psfm_ground_truth.hip; the two per-element rules are csrc/psfm_ground_truth.h).
  * psfm_traj_eval_counts     motion_seg/eval_traj_iou.py:79-115 (per_img_traj_metrics) reduced to what its four metrics are functions
  *                           of: per frame, the counts tp, fp, fn, tn over the labelled points of that frame.  A point (x, y) f64 is

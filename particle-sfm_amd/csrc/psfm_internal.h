@@ -220,6 +220,12 @@ struct psfm_ctx {
     int db_n_img = 0;
     bool db_valid = false;
     bool db_src_live = false;            // the match tables are still the ones the database tables were built from (psfm_database_compact_again)
+    // psfm_sparse_depth (psfm_sparse_depth.hip): winner map | point rows of the observations | descriptors | flags
+    PsfmBuf sd_ws;
+    int64_t sd_budget = 1ll << 30;       // bytes of maps + winners (12 per pixel) the callers put into one call; 0: no limit
+    bool sd_timing = false;              // record events around the fill, the winner pass and the store pass
+    hipEvent_t sd_events[4] = {nullptr, nullptr, nullptr, nullptr};
+    double sd_ms[3] = {0.0, 0.0, 0.0};
     PsfmBuf gt_flag;                     // psfm_traj_vote_labels (psfm_ground_truth.hip): a present point outside the image
     hipStream_t side_stream = nullptr;   // flow_check of psfm_connect runs here, ahead of the frame loop
     hipStream_t copy_stream = nullptr;   // psfm_load_flo_stack: H2D copies out of the pinned ring

@@ -31,6 +31,8 @@ EXPORTS = [
     "psfm_traj_eval_counts", "psfm_traj_vote_labels",
     "psfm_labels_set", "psfm_matches_to_database", "psfm_database_copy", "psfm_database_chunk_rows",
     "psfm_database_compact_again",
+    "psfm_sparse_depth", "psfm_sparse_depth_sort_ids", "psfm_ctx_set_sparse_depth", "psfm_ctx_get_sparse_depth_budget",
+    "psfm_sparse_depth_last_ms", "psfm_colmap_points3d_count", "psfm_colmap_points3d_scan",
 ]
 
 
@@ -127,6 +129,13 @@ def lib():
     L.psfm_database_copy.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.psfm_database_chunk_rows.argtypes = []
     L.psfm_database_compact_again.argtypes = [vp, vp]
+    L.psfm_sparse_depth.argtypes = [vp, vp, vp, i64, vp, i32, vp, vp, vp, i64, vp, ctypes.POINTER(i64), vp]
+    L.psfm_sparse_depth_sort_ids.argtypes = [vp, vp, i64, vp, vp, vp]
+    L.psfm_ctx_set_sparse_depth.argtypes = [vp, i64, i32]
+    L.psfm_ctx_get_sparse_depth_budget.argtypes = [vp, ctypes.POINTER(i64)]
+    L.psfm_sparse_depth_last_ms.argtypes = [vp, ctypes.POINTER(f64)]
+    L.psfm_colmap_points3d_count.argtypes = [vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
+    L.psfm_colmap_points3d_scan.argtypes = [vp, ctypes.c_uint64, vp, vp, vp, vp]
     L.psfm_shard_begin.argtypes = [vp, i32, i32, i32, i32, i64, i64, i32, vp, i64, vp]
     L.psfm_shard_step.argtypes = [vp, vp, vp, i32, vp]
     L.psfm_shard_solve_export.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp]
@@ -210,6 +219,16 @@ class Context:
         check(lib().psfm_solver_launches(self._h, ctypes.byref(r), ctypes.byref(g), ctypes.byref(it)))
         out.update({"resident_launches": r.value, "resident_giveups": g.value, "iteration_launches": it.value})
         return out
+
+    def set_sparse_depth(self, budget_bytes=1 << 30, timing=False):
+        """psfm_sfm.convert: bytes of depth maps + winner maps (12 per pixel) one psfm_sparse_depth call may take (0: no limit; one
+        image always goes through); timing: events around the zero fill, the winner pass and the store pass (sparse_depth_ms)."""
+        check(lib().psfm_ctx_set_sparse_depth(self._h, int(budget_bytes), int(bool(timing))))
+
+    def sparse_depth_ms(self):
+        ms = (ctypes.c_double * 3)()
+        check(lib().psfm_sparse_depth_last_ms(self._h, ms))
+        return {"fill_ms": ms[0], "winner_ms": ms[1], "store_ms": ms[2]}
 
     def set_profiling(self, enable):
         check(lib().psfm_ctx_set_profiling(self._h, int(enable)))   # 0 off, 1 every launch, N>1 every N-th chain_step
