@@ -118,6 +118,30 @@ psfm_status psfm_ctx_set_capacity(psfm_ctx* ctx, double lane_factor, double traj
  * Results are identical in every mode.  track_optimize always uses one launch per frame (the solves sit in between). */
 psfm_status psfm_ctx_set_chain_mode(psfm_ctx* ctx, int mode);
 
+/* Motion-boundary termination of trajectories (trajectory.py:39-43,51-53 and the commented kill rule of :60, "for some in-the-wilds,
+ * we use motion boundary"): enable != 0 makes psfm_track / psfm_connect on this context kill a track when
+ * !valid | occ_cond | mb_cond, with mb_cond a second bilinear verdict (> 0.1) over motion_boundary(flow, thres) of the frame's own
+ * flow.  Default off: nothing differs from the shipped rule.  thres must be finite and >= 0 (PSFM_ERR_ARG otherwise).
+ * With the option on
+ *   - both entry points run the recurrence with one launch per frame whatever psfm_ctx_set_chain_mode says (info->chain_mode == 1);
+ *     the occlusion and motion-boundary masks travel as one byte per pixel in a stack owned by the context, built by one launch
+ *     from the flows and the COMPLETE occlusion maps -- `occ` of the caller stays 0/1;
+ *   - track_optimize runs a frame as two launches (chain step, then the solve in any of its forms);
+ *   - psfm_connect_batch and psfm_shard_begin refuse the context (PSFM_ERR_ARG). */
+psfm_status psfm_ctx_set_motion_boundary(psfm_ctx* ctx, int enable, float thres);
+
+/* trajectory.py:39-43 for a stack of flow maps: mb_out[f,y,x] = 1 where the flow gradient of pixel (x, y) of map f exceeds
+ * thres x the flow's norm, else 0 (the rule, operation by operation: csrc/psfm_motion_boundary.h).
+ *   flows (n,H,W,2) f32      mb_out (n,H,W) u8
+ * Asynchronous on `stream`; identical calls give identical bytes. */
+psfm_status psfm_motion_boundary(psfm_ctx* ctx, const float* flows, int n, int h, int w, float thres, uint8_t* mb_out, void* stream);
+
+/* The kill maps psfm_track / psfm_connect sample with the option on, from the same launch that builds them there:
+ * kill_out[f,y,x] = (occ[f,y,x] != 0) | motion boundary << 1.  occ (n,H,W) u8 is read only; kill_out must not alias it.
+ * Asynchronous on `stream`. */
+psfm_status psfm_kill_map(psfm_ctx* ctx, const float* flows, const uint8_t* occ, int n, int h, int w, float thres, uint8_t* kill_out,
+                          void* stream);
+
 /* How psfm_track / psfm_connect run the path-consistency solve of a frame (track_optimize.py:49-50 ->
  * trajectory_optimize.cpp:74-82) -- the results do not depend on it:
  *   mode 0 (default) adaptive: the FUSED solve -- one launch per frame (the frame's chain step included) that speculates k

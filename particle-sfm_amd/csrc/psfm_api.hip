@@ -37,6 +37,7 @@ void psfm_gate_waiters_add(int device, int d) { g_dev_waiters[device & 15].fetch
 static int psfm_wants_persist(psfm_ctx* c, bool optimize, int h, int w, int ratio, bool fused)
 {
     if (c->chain_mode == 1 || ratio < 1 || !psfm_frame_ok(h, w)) return 0;
+    if (c->mb_enable && !optimize) return 0;     // the motion-boundary verdict lives in the per-frame chain step only
     // track_optimize: no persistent frame loop, but solves that reject steps run their trust-region loop as one persistent
     // launch (psfm_pc_resident_kernel) when the call has the device to itself -- take the gate if it is free.  A context with a
     // resident budget runs those launches on its share of the device's block slots beside other contexts': shared gate
@@ -178,7 +179,7 @@ extern "C" psfm_status psfm_ctx_destroy(psfm_ctx* c)
                        &c->sol_partials, &c->sol_ctrl, &c->sol_misc, &c->sol_stats, &c->sol_fused, &c->sol_bar, &c->sol_list, &c->occ_own, &c->occ2_own,
                        &c->handoff, &c->seg_info, &c->seg_table, &c->persist_bar, &c->batch_tab, &c->batch_ws, &c->batch_fc, &c->win_ws, &c->flt_ids, &c->flt_birth, &c->flt_len, &c->flt_off, &c->flt_xy,
                        &c->mt_kp_off, &c->mt_q, &c->mt_pts, &c->mt_kp_ind, &c->mt_kp_xy, &c->mt_moff, &c->mt_keys, &c->mt_rows, &c->mt_gid, &c->mt_pairs,
-                       &c->lb_state, &c->lb_first, &c->lb_flag, &c->lb_ws, &c->lb_ids, &c->lb_off, &c->lb_frames, &c->lb_xy, &c->lb_labels, &c->gt_flag,
+                       &c->lb_state, &c->lb_first, &c->lb_flag, &c->lb_ws, &c->lb_ids, &c->lb_off, &c->lb_frames, &c->lb_xy, &c->lb_labels, &c->gt_flag, &c->kill,
                        &c->db_kp, &c->db_pairs, &c->db_rows, &c->db_ws, &c->sd_ws};
     for (auto b : bufs) b->release();
     for (hipEvent_t e : c->sd_events) if (e) (void)hipEventDestroy(e);
@@ -472,7 +473,8 @@ static psfm_status psfm_track_impl(psfm_ctx* c, const float* flows, const uint8_
     c->pc_giveups = 0;
 
     // ---- track mode: the whole recurrence as ONE persistent launch when every lane can be resident at once ----
-    if (!optimize && c->chain_mode != 1) {
+    const bool mb = c->mb_enable;     // psfm_ctx_set_motion_boundary: per-frame launches with the second verdict, whatever the chain mode
+    if (!optimize && c->chain_mode != 1 && !mb) {
         const int maxb = psfm_persist_max_blocks(c);
         const int64_t need_blocks = (d.G + 255) / 256;
         if (maxb > 0 && need_blocks <= maxb && device_is_ours) {   // (not ours: another psfm call is in flight on this device)
@@ -547,6 +549,14 @@ static psfm_status psfm_track_impl(psfm_ctx* c, const float* flows, const uint8_
                                              const_cast<uint8_t*>(occ) + (size_t)f * occ_pitch, nullptr, s)) != PSFM_OK) return st;
         c->prof.end(s);
     }
+    if (mb) {
+        // the kill maps of the sequence -- bit 0 the occlusion map, bit 1 motion_boundary(flow) -- in ONE launch, from the COMPLETE
+        // occlusion maps (psfm_connect: every chunk of the side stream; the stride-2 maps keep their pipeline).  `occ` stays 0/1.
+        if ((st = c->kill.ensure((size_t)n_flows * (size_t)P)) != PSFM_OK) return st;
+        if (pipe && (st = pipe->need(n_flows - 1, false, s)) != PSFM_OK) return st;
+        if (occ_pitch != P) { psfm_set_error("psfm_track: motion boundary needs densely packed occlusion maps"); return PSFM_ERR_ARG; }
+        if ((st = psfm_launch_motion_boundary(flows, occ, n_flows, h, w, c->mb_thres, c->kill.as<uint8_t>(), s)) != PSFM_OK) return st;
+    }
     if ((st = psfm_launch_track_init(c, d, s)) != PSFM_OK) return st;
     int64_t total_iters = 0;
     // Frame loop.  In track_optimize mode nothing returns to the host inside a window of PSFM_CHECK frames: each
@@ -575,7 +585,8 @@ static psfm_status psfm_track_impl(psfm_ctx* c, const float* flows, const uint8_
     // PSFM_SEQ=0: host-paced frame kernels (one per frame, stall + redo when a solve needs more iterations than speculated)
     static const bool merge = !(getenv("PSFM_MERGE_FRAME") && atoi(getenv("PSFM_MERGE_FRAME")) == 0);
     const bool seq_env = !(getenv("PSFM_SEQ") && atoi(getenv("PSFM_SEQ")) == 0);
-    bool seq_ok = optimize && merge && seq_env && unroll_fixed == 0;
+    // (motion boundary: the two-launch frame -- the merged and the device-paced kernels do not form the second verdict)
+    bool seq_ok = optimize && merge && seq_env && unroll_fixed == 0 && !mb;
     int launch_id = 0;            // device-paced windows: id of the next psfm_seq_kernel launch (== PsfmCounters::pc_owner)
     int idle_windows = 0;         // ... consecutive windows in which no frame completed (the device inside one long solve)
     bool pc_in_step = true;       // the device's program counter is where the host thinks it is (track_init: frame 1, launch 0)
@@ -724,14 +735,15 @@ static psfm_status psfm_track_impl(psfm_ctx* c, const float* flows, const uint8_
         // one launch = births of frame f (new_traj_all) + chain step f (step_forward, extend_all)
         if (pipe && (st = pipe->need(f, false, s)) != PSFM_OK) return st;
         const bool solve_now = optimize && f + 1 >= 2;   // track_optimize.py:49-50
-        if (solve_now && fused_now && merge) {
+        if (solve_now && fused_now && merge && !mb) {
             // ONE launch: chain step of the frame + the fused solve of its tracks
             if (pipe && (st = pipe->need(f - 1, true, s)) != PSFM_OK) return st;
             st = psfm_launch_frame(c, d, flows + (size_t)(f - 1) * P * 2, flows + (size_t)f * P * 2, flows_f2 + (size_t)(f - 1) * P * 2,
                                    occ + (size_t)f * occ_pitch, occ_s2 + (size_t)(f - 1) * P, f, c->solver_K > 0 ? c->solver_K : c->solve_K, s);
             if (st != PSFM_OK) return st;
         } else {
-            st = psfm_launch_chain_step(c, d, flows + (size_t)f * P * 2, occ + (size_t)f * occ_pitch, f, optimize, s);
+            if (mb) st = psfm_launch_chain_step_mb(c, d, flows + (size_t)f * P * 2, c->kill.as<uint8_t>() + (size_t)f * P, f, optimize, s);
+            else st = psfm_launch_chain_step(c, d, flows + (size_t)f * P * 2, occ + (size_t)f * occ_pitch, f, optimize, s);
             if (st != PSFM_OK) return st;
             if (solve_now) {
                 if (pipe && (st = pipe->need(f - 1, true, s)) != PSFM_OK) return st;
@@ -810,7 +822,7 @@ extern "C" psfm_status psfm_connect(psfm_ctx* c, const float* flows_f, const flo
     // written through to HBM by their producers and first read by other XCDs a few barriers later; a cache line must
     // not straddle two maps, hence the 128-byte pitch (caller-provided buffers qualify when H*W is a multiple of 128
     // and the buffer is 128-byte aligned).
-    if (gate.exclusive && !optimize && (!occ || (P % 128 == 0 && ((uintptr_t)occ & 127) == 0))) {
+    if (gate.exclusive && !optimize && !c->mb_enable && (!occ || (P % 128 == 0 && ((uintptr_t)occ & 127) == 0))) {
         int64_t pitch = (int64_t)P;
         if (!occ) {
             pitch = (int64_t)((P + 127) / 128 * 128);

@@ -77,6 +77,11 @@ extern "C" psfm_status psfm_connect_batch(psfm_ctx* const* ctxs, int n_seq, cons
     for (int i = 0; i < n_seq; ++i) if (ctxs[i]) ctxs[i]->res_gen++;
     for (int i = 0; i < n_seq; ++i) {
         if (!ctxs[i] || ctxs[i]->device != ctxs[0]->device) { psfm_set_error("psfm_connect_batch: context %d is NULL or on another device", i); return PSFM_ERR_ARG; }
+        if (ctxs[i]->mb_enable) {
+            psfm_set_error("psfm_connect_batch: context %d has psfm_ctx_set_motion_boundary on; the batched frame launches do not form the "
+                           "motion-boundary verdict -- run its sequence through psfm_connect", i);
+            return PSFM_ERR_ARG;
+        }
         for (int j = 0; j < i; ++j) if (ctxs[j] == ctxs[i]) { psfm_set_error("psfm_connect_batch: context %d given twice (one per sequence)", i); return PSFM_ERR_ARG; }
         if (n_flows[i] < 1 || !flows_f[i] || !flows_b[i] || (optimize && n_flows[i] > 1 && (!flows_f2[i] || !flows_b2[i]))) {
             psfm_set_error("psfm_connect_batch: bad sequence %d (n_flows=%d)", i, n_flows[i]);

@@ -111,7 +111,10 @@ __device__ __forceinline__ PsfmStepLoads psfm_step_issue(const A& a, double2 p)
     return L;
 }
 
-template <class A>
+// MB (the motion-boundary option, trajectory.py:51-53,60): the mask bytes are KILL-MAP bytes -- bit 0 occlusion, bit 1 motion boundary
+// (psfm_motion_boundary.h) -- and give two verdicts through the same taps, each compared on its own: alive = valid & !occ & !mb.
+// (One verdict over occ | mb is another rule: two taps of weight 0.06, one occluded, one on a boundary, would kill.)
+template <bool MB = false, class A>
 __device__ __forceinline__ PsfmStep psfm_step_finish(const A& a, double2 p, const PsfmStepLoads& L)
 {
     const PsfmTaps t = psfm_taps_fast((float)p.x, (float)p.y, a.cw, a.ch, a.rcw, a.rch, a.H, a.W);
@@ -122,14 +125,21 @@ __device__ __forceinline__ PsfmStep psfm_step_finish(const A& a, double2 p, cons
     const float z = 0.0f;
     const float fx = psfm_blend(inw ? L.fnw.x : z, ine ? L.fne.x : z, isw ? L.fsw.x : z, ise ? L.fse.x : z, t);
     const float fy = psfm_blend(inw ? L.fnw.y : z, ine ? L.fne.y : z, isw ? L.fsw.y : z, ise ? L.fse.y : z, t);
-    const float oc = psfm_blend((inw & (L.onw != 0)) ? 1.0f : z, (ine & (L.one != 0)) ? 1.0f : z,
-                                (isw & (L.osw != 0)) ? 1.0f : z, (ise & (L.ose != 0)) ? 1.0f : z, t);
+    const unsigned ob = MB ? 1u : ~0u;     // the occlusion bit(s) of a mask byte
+    const float oc = psfm_blend((inw & ((L.onw & ob) != 0)) ? 1.0f : z, (ine & ((L.one & ob) != 0)) ? 1.0f : z,
+                                (isw & ((L.osw & ob) != 0)) ? 1.0f : z, (ise & ((L.ose & ob) != 0)) ? 1.0f : z, t);
+    bool on_boundary = false;
+    if (MB) {
+        const float mb = psfm_blend((inw & ((L.onw & 2u) != 0)) ? 1.0f : z, (ine & ((L.one & 2u) != 0)) ? 1.0f : z,
+                                    (isw & ((L.osw & 2u) != 0)) ? 1.0f : z, (ise & ((L.ose & 2u) != 0)) ? 1.0f : z, t);
+        on_boundary = mb > 0.1f;
+    }
     const double nx = p.x + (double)fx, ny = p.y + (double)fy;
     const bool valid = (nx > 0.0) & (nx < (double)(a.W - 1)) & (ny > 0.0) & (ny < (double)(a.H - 1));
     PsfmStep s;
     s.next = make_double2(nx, ny);
     s.flow = make_float2(fx, fy);
-    s.alive = valid & !(oc > 0.1f);
+    s.alive = valid & !(oc > 0.1f) & !on_boundary;
     return s;
 }
 

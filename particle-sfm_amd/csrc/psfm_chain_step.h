@@ -126,7 +126,8 @@ __device__ __forceinline__ int psfm_xcd_tile(int b, int n)
 // (PsfmCounters::n_lanes_snap -- every block of the launch must agree on which blocks take part in the solve's tickets,
 // and n_lanes itself grows while the launch runs), p0 is loaded with the other early loads, and `o` is filled.
 // Returns false when the block has nothing to do (stalled sequence / tile beyond the lanes and the grid).
-template <int R, bool OPT, bool MERGED>
+// MB: `a.occ` is the frame's kill map and the step forms the motion-boundary verdict beside the occlusion verdict (psfm_step_finish<MB>).
+template <int R, bool OPT, bool MERGED, bool MB = false>
 __device__ __forceinline__ bool psfm_chain_step_body(const PsfmChainArgs& a, PsfmChainOut& o)
 {
     __shared__ int s_births[PSFM_CHAIN_NSEG], s_pend[PSFM_CHAIN_NSEG];
@@ -339,7 +340,7 @@ __device__ __forceinline__ bool psfm_chain_step_body(const PsfmChainArgs& a, Psf
         }
         // ---- (B) results of the lane's step ----
         if (live[u]) {
-            const PsfmStep s1 = psfm_step_finish(a, p1[u], l1[u]);
+            const PsfmStep s1 = psfm_step_finish<MB>(a, p1[u], l1[u]);
             if (MERGED && u == 0 && s1.alive && bf[u] <= frame - 1) { o.solve = true; o.p0 = p0m; o.p1 = p1[u]; o.p2 = s1.next; }
             if (s1.alive) {
                 psfm_st(a.log_next, (unsigned)i * 16u, s1.next);
@@ -358,7 +359,7 @@ __device__ __forceinline__ bool psfm_chain_step_body(const PsfmChainArgs& a, Psf
         int g = g2, L = L2;
         double2 pg = p2;
         if (PSFM_LPT == 1 || t == tid) {   // (one lane per thread: at most one newborn per thread)
-            s2 = psfm_step_finish(a, p2, l2);
+            s2 = psfm_step_finish<MB>(a, p2, l2);
         } else {
             int before = 0, pbefore = 0;
             g = -1; L = -1;
@@ -372,7 +373,7 @@ __device__ __forceinline__ bool psfm_chain_step_body(const PsfmChainArgs& a, Psf
             const int gy = (int)psfm_fastdiv((unsigned)g, a.gwdiv), gx = g - gy * a.GW;
             pg = make_double2((double)(gx * ratio), (double)(gy * ratio));
             const PsfmStepLoads lx = psfm_step_issue(a, pg);
-            s2 = psfm_step_finish(a, pg, lx);
+            s2 = psfm_step_finish<MB>(a, pg, lx);
         }
         if (t >= matched) {                  // popped / fresh lane (t < matched: inherited from a just-died track)
             const int qq = t - matched;

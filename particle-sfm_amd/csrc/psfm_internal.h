@@ -155,6 +155,9 @@ struct psfm_ctx {
     PsfmBuf persist_bar;  // barrier: 64 arrival counters, 1 top counter, 64 release flags (128 B apart)
     int persist_max_blocks = -1;   // resident 256-thread blocks on this device (-1: not queried yet)
     int chain_mode = 0;            // 0 auto, 1 per-frame launches only, 2 persistent loop required
+    bool mb_enable = false;        // psfm_ctx_set_motion_boundary: tracks also die on motion boundaries (per-frame launches only)
+    float mb_thres = 0.02f;
+    PsfmBuf kill;                  // ... the kill maps of the sequence: (n_flows,H,W) u8, bit 0 occlusion, bit 1 motion boundary
     void* host_seg = nullptr;      // pinned staging for seg_info / seg_table
     size_t host_seg_bytes = 0;
     // finalize workspace + result
@@ -268,6 +271,13 @@ psfm_status psfm_track_alloc(psfm_ctx* c, const PsfmTrackDims& d);
 psfm_status psfm_launch_track_init(psfm_ctx* c, const PsfmTrackDims& d, hipStream_t s);
 psfm_status psfm_launch_chain_step(psfm_ctx* c, const PsfmTrackDims& d, const float* flow, const uint8_t* occ,
                                    int frame, bool optimize, hipStream_t s);
+
+// ---- motion boundary (psfm_motion_boundary.hip) ----------------------------------------------
+// out[f,y,x] = motion-boundary bit of pixel (x, y) of flow map f: 0/1 when occ == NULL, else (occ != 0) | mb << 1 (the kill map)
+psfm_status psfm_launch_motion_boundary(const float* flows, const uint8_t* occ, int n, int h, int w, float thres, uint8_t* out, hipStream_t s);
+// psfm_launch_chain_step with the motion-boundary verdict: `kill` is the frame's kill map
+psfm_status psfm_launch_chain_step_mb(psfm_ctx* c, const PsfmTrackDims& d, const float* flow, const uint8_t* kill, int frame, bool optimize,
+                                      hipStream_t s);
 
 // ---- batch: B same-shape sequences per launch (psfm_batch.hip; kernels beside their single-sequence forms) --------------------
 #define PSFM_BATCH_MAX 64

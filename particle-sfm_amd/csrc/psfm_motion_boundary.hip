@@ -1,0 +1,252 @@
+// psfm_motion_boundary.hip -- gfx950 kernels of the motion-boundary option (psfm_ctx_set_motion_boundary):
+//   the mask of trajectory.py:39-43 over a whole flow stack, alone (psfm_motion_boundary) or folded with the occlusion maps into the
+//   KILL MAP the chain step samples (bit 0 occlusion, bit 1 motion boundary), and the chain step with the second verdict
+//   (psfm_chain_step_body<.., MB = true>: trajectory.py:51-53 and the kill rule of :60).
+// The per-pixel rule lives in psfm_motion_boundary.h; the host build of the CPU suite compiles the same text.
+#include "psfm_device.h"
+#include <hip/hip_ext.h>
+#include <stdlib.h>
+
+#include "psfm_internal.h"
+#include "psfm_motion_boundary.h"
+#include "psfm_chain_step.h"
+
+#define PSFM_MB_BLOCK 256
+#define PSFM_MB_PPL 4             // pixels per lane: 32 bytes of flow = two 16-byte loads, 4 result bytes = one 32-bit store
+
+// ------------------------------------------------------------------------------------------------
+// The mask as a stream.  Algorithmic bytes per pixel: 8 (flow) [+ 1 (occlusion byte)] + 1 (result); the south neighbours are the
+// row the same XCD streams W / 4 lanes later, the east neighbour of a lane's last pixel is the next lane's first.
+//
+// The stack is ONE run of N = n H W pixels and lane g owns pixels 4g .. 4g + 3 of it, wherever rows and frames end: the lane's own
+// pixels are always 32 aligned bytes (flows 16-byte aligned: the launcher checks), the results 4 aligned bytes.  A launch has
+// blockIdx.y = frame f and covers the lanes whose FIRST pixel lies in frame f -- [ceil(f P / 4), ceil((f + 1) P / 4)) -- so a
+// lane's position inside its frame is 32-bit arithmetic; its last pixels may belong to frame f + 1 (P not a multiple of 4).
+//   own pixels     2 x 16 bytes
+//   row below      2 x 16 bytes at + W pixels when W is even (the address is then 16-byte aligned), 4 x 8 bytes otherwise; a pixel
+//                  of a frame's last row has dy = 0 and the loaded value is never used (the unguarded forms read the next frame's
+//                  first row there; the last lanes of the stack, which have nothing behind them, take guarded 8-byte loads)
+//   east           pixel j + 1 of the lane; for the last one 8 bytes more (the next lane's first pixel)
+// blockIdx.x -> chunk of 256 lanes through the XCD banding of flow_check (psfm_track.hip): blocks go to the eight XCDs round-robin,
+// so each XCD takes one contiguous band of rows and finds the row below in its own L2.
+// ------------------------------------------------------------------------------------------------
+struct PsfmMbArgs {
+    const float2* flows; const uint8_t* occ; uint8_t* out;
+    int H, W, P;                  // P = H W < 2^29 (psfm_frame_ok)
+    int n, frame0;                // frames of the stack; frame of blockIdx.y == 0
+    float thres;
+    int chunks, xcd_per;          // 256-lane chunks per frame (ceil((P / 4 + 1) / 256)); > 0: chunks per XCD band
+    int out_al4;                  // out (and occ) 4-byte aligned: results leave as one 32-bit store
+    PsfmFastDiv wdiv;
+};
+
+// One lane's four pixels from q0 on (r0: the first one's index in its frame).  FAST (decided per block, from uniform values): every
+// lane of the block has its four pixels, the pixel behind them and the four pixels one row below inside the stack, and the byte
+// buffers are 4-byte aligned -- nothing is guarded, so all loads are issued back to back behind one wait.  Otherwise (the last block
+// of a frame's lanes, the tail of the stack, unaligned byte buffers) every access is checked.
+template <bool HAS_OCC, bool WEVEN, bool FAST>
+__device__ __forceinline__ void psfm_mb_lane(const PsfmMbArgs& a, int64_t q0, int r0, int64_t N)
+{
+    const float2* __restrict__ Fq = a.flows + q0;
+    const bool whole = FAST || q0 + PSFM_MB_PPL <= N;       // all four pixels exist
+    const bool words = FAST || (whole & (a.out_al4 != 0));  // the four bytes travel as one 32-bit word
+    const float2 z2 = make_float2(0.0f, 0.0f);
+
+    // ---- position of every pixel in its frame ----
+    int x[PSFM_MB_PPL], y[PSFM_MB_PPL];
+    y[0] = (int)psfm_fastdiv((unsigned)r0, a.wdiv); x[0] = r0 - y[0] * a.W;
+#pragma unroll
+    for (int j = 1; j < PSFM_MB_PPL; ++j) {
+        x[j] = x[j - 1] + 1; y[j] = y[j - 1];
+        if (x[j] == a.W) { x[j] = 0; ++y[j]; }
+        if (y[j] == a.H) y[j] = 0;                           // first row of the next frame
+    }
+
+    // ---- loads ----
+    float2 own[PSFM_MB_PPL + 1], below[PSFM_MB_PPL];
+    if (whole) {
+        const float4 lo = *(const float4*)Fq, hi = *(const float4*)(Fq + 2);
+        own[0] = make_float2(lo.x, lo.y); own[1] = make_float2(lo.z, lo.w);
+        own[2] = make_float2(hi.x, hi.y); own[3] = make_float2(hi.z, hi.w);
+    } else {
+#pragma unroll
+        for (int j = 0; j < PSFM_MB_PPL; ++j) own[j] = q0 + j < N ? Fq[j] : z2;
+    }
+    own[PSFM_MB_PPL] = (FAST || q0 + PSFM_MB_PPL < N) ? Fq[PSFM_MB_PPL] : z2;
+    if (WEVEN && (FAST || q0 + a.W + PSFM_MB_PPL <= N)) {
+        const float4 lo = *(const float4*)(Fq + a.W), hi = *(const float4*)(Fq + a.W + 2);
+        below[0] = make_float2(lo.x, lo.y); below[1] = make_float2(lo.z, lo.w);
+        below[2] = make_float2(hi.x, hi.y); below[3] = make_float2(hi.z, hi.w);
+    } else {
+#pragma unroll
+        for (int j = 0; j < PSFM_MB_PPL; ++j)      // (y + 1 < H: the pixel below is in the stack)
+            below[j] = (FAST || ((q0 + j < N) & (y[j] + 1 < a.H))) ? Fq[a.W + j] : z2;
+    }
+    unsigned ob = 0;                                         // the lane's four occlusion bytes
+    if (HAS_OCC) {
+        if (words) ob = *(const unsigned*)(a.occ + q0);
+        else {
+#pragma unroll
+            for (int j = 0; j < PSFM_MB_PPL; ++j) if (q0 + j < N) ob |= (unsigned)a.occ[q0 + j] << (8 * j);
+        }
+    }
+
+    // ---- verdicts ----
+    unsigned res = 0;
+#pragma unroll
+    for (int j = 0; j < PSFM_MB_PPL; ++j) {
+        unsigned v = psfm_mb_px(own[j], own[j + 1], x[j] + 1 < a.W, below[j], y[j] + 1 < a.H, a.thres);
+        if (HAS_OCC) v = (((ob >> (8 * j)) & 0xffu) != 0 ? PSFM_KILL_OCC : 0u) | (v ? PSFM_KILL_MB : 0u);
+        res |= v << (8 * j);
+    }
+    if (words) *(unsigned*)(a.out + q0) = res;
+    else {
+#pragma unroll
+        for (int j = 0; j < PSFM_MB_PPL; ++j) if (q0 + j < N) a.out[q0 + j] = (uint8_t)(res >> (8 * j));
+    }
+}
+
+template <bool HAS_OCC, bool WEVEN>
+__global__ __launch_bounds__(PSFM_MB_BLOCK) void psfm_mb_kernel(PsfmMbArgs a)
+{
+    const int bx = (int)blockIdx.x;
+    const int chunk = a.xcd_per > 0 ? (bx & 7) * a.xcd_per + (bx >> 3) : bx;
+    if (chunk >= a.chunks) return;
+    const int f = a.frame0 + (int)blockIdx.y;
+    const int64_t N = (int64_t)a.n * a.P;
+    const int64_t F0 = (int64_t)f * a.P;
+    const int64_t g_lo = (F0 + 3) >> 2, g_hi = (F0 + a.P + 3) >> 2;
+    const int64_t g_blk = g_lo + (int64_t)chunk * PSFM_MB_BLOCK;          // the block's first lane
+    const int64_t g = g_blk + threadIdx.x;
+    const int64_t q0 = g * PSFM_MB_PPL;                                   // < N when g < g_hi: g_hi <= ceil(N / 4)
+    const int r0 = (int)(q0 - F0);                                        // in [0, P) when g < g_hi
+    // (block-uniform) the block's last lane is a lane of the frame, and the furthest byte it touches -- pixel q0 + W + 3 -- exists
+    const int64_t g_last = g_blk + PSFM_MB_BLOCK - 1;
+    const bool fast = (a.out_al4 != 0) & (g_last < g_hi) & (g_last * PSFM_MB_PPL + a.W + 2 * PSFM_MB_PPL <= N);
+    if (fast) {
+        psfm_mb_lane<HAS_OCC, WEVEN, true>(a, q0, r0, N);
+    } else {
+        if (g >= g_hi) return;
+        psfm_mb_lane<HAS_OCC, WEVEN, false>(a, q0, r0, N);
+    }
+}
+
+// one pixel per thread, for a flow stack that is not 16-byte aligned (no caller of the package has one)
+template <bool HAS_OCC>
+__global__ __launch_bounds__(PSFM_MB_BLOCK) void psfm_mb_px_kernel(PsfmMbArgs a)
+{
+    const int p = (int)blockIdx.x * PSFM_MB_BLOCK + (int)threadIdx.x;
+    if (p >= a.P) return;
+    const int64_t base = (int64_t)(a.frame0 + (int)blockIdx.y) * a.P;
+    const int y = (int)psfm_fastdiv((unsigned)p, a.wdiv), x = p - y * a.W;
+    unsigned v = psfm_mb_at(a.flows + base, x, y, a.H, a.W, a.thres);
+    if (HAS_OCC) v = (a.occ[base + p] != 0 ? PSFM_KILL_OCC : 0u) | (v ? PSFM_KILL_MB : 0u);
+    a.out[base + p] = (uint8_t)v;
+}
+
+psfm_status psfm_launch_motion_boundary(const float* flows, const uint8_t* occ, int n, int h, int w, float thres, uint8_t* out, hipStream_t s)
+{
+    if (n <= 0) return PSFM_OK;
+    PsfmMbArgs a;
+    a.flows = (const float2*)flows; a.occ = occ; a.out = out;
+    a.H = h; a.W = w; a.P = h * w; a.n = n; a.thres = thres;
+    a.wdiv = psfm_fastdiv_make((unsigned)w);
+    a.out_al4 = (((uintptr_t)out % 4) == 0 && (!occ || ((uintptr_t)occ % 4) == 0)) ? 1 : 0;
+    const bool vec = ((uintptr_t)flows % 16) == 0;
+    const int lanes = a.P / PSFM_MB_PPL + 1;                 // of one frame, at most
+    a.chunks = vec ? (lanes + PSFM_MB_BLOCK - 1) / PSFM_MB_BLOCK : (a.P + PSFM_MB_BLOCK - 1) / PSFM_MB_BLOCK;
+    a.xcd_per = (vec && a.chunks >= 64) ? (a.chunks + 7) / 8 : 0;
+    const unsigned gx = (unsigned)(a.xcd_per > 0 ? 8 * a.xcd_per : a.chunks);
+    for (int f0 = 0; f0 < n; f0 += 32768) {                  // (gridDim.y < 65536)
+        a.frame0 = f0;
+        const dim3 grid(gx, (unsigned)(n - f0 < 32768 ? n - f0 : 32768)), block(PSFM_MB_BLOCK);
+        if (vec) {
+            const bool weven = (w & 1) == 0;
+            if (occ && weven) hipLaunchKernelGGL((psfm_mb_kernel<true, true>), grid, block, 0, s, a);
+            else if (occ) hipLaunchKernelGGL((psfm_mb_kernel<true, false>), grid, block, 0, s, a);
+            else if (weven) hipLaunchKernelGGL((psfm_mb_kernel<false, true>), grid, block, 0, s, a);
+            else hipLaunchKernelGGL((psfm_mb_kernel<false, false>), grid, block, 0, s, a);
+        } else {
+            if (occ) hipLaunchKernelGGL(psfm_mb_px_kernel<true>, grid, block, 0, s, a);
+            else hipLaunchKernelGGL(psfm_mb_px_kernel<false>, grid, block, 0, s, a);
+        }
+    }
+    PSFM_HIP(hipGetLastError());
+    return PSFM_OK;
+}
+
+extern "C" psfm_status psfm_motion_boundary(psfm_ctx* c, const float* flows, int n, int h, int w, float thres, uint8_t* mb_out, void* stream)
+{
+    if (!c) { psfm_set_error("ctx is NULL"); return PSFM_ERR_ARG; }
+    PSFM_HIP(hipSetDevice(c->device));
+    PsfmGate gate(c->device, 0);
+    if (n < 0 || !psfm_frame_ok(h, w) || (n > 0 && (!flows || !mb_out))) {
+        psfm_set_error("psfm_motion_boundary: bad argument (n=%d h=%d w=%d)", n, h, w);
+        return PSFM_ERR_ARG;
+    }
+    return psfm_launch_motion_boundary(flows, nullptr, n, h, w, thres, mb_out, (hipStream_t)stream);
+}
+
+extern "C" psfm_status psfm_kill_map(psfm_ctx* c, const float* flows, const uint8_t* occ, int n, int h, int w, float thres, uint8_t* kill_out,
+                                     void* stream)
+{
+    if (!c) { psfm_set_error("ctx is NULL"); return PSFM_ERR_ARG; }
+    PSFM_HIP(hipSetDevice(c->device));
+    PsfmGate gate(c->device, 0);
+    if (n < 0 || !psfm_frame_ok(h, w) || (n > 0 && (!flows || !occ || !kill_out))) {
+        psfm_set_error("psfm_kill_map: bad argument (n=%d h=%d w=%d)", n, h, w);
+        return PSFM_ERR_ARG;
+    }
+    return psfm_launch_motion_boundary(flows, occ, n, h, w, thres, kill_out, (hipStream_t)stream);
+}
+
+extern "C" psfm_status psfm_ctx_set_motion_boundary(psfm_ctx* c, int enable, float thres)
+{
+    if (!c) { psfm_set_error("ctx is NULL"); return PSFM_ERR_ARG; }
+    if (!(thres >= 0.0f) || thres == INFINITY) {             // (NaN fails the first comparison)
+        psfm_set_error("psfm_ctx_set_motion_boundary: thres must be finite and >= 0");
+        return PSFM_ERR_ARG;
+    }
+    c->mb_enable = enable != 0;
+    c->mb_thres = thres;
+    return PSFM_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The chain step with the motion-boundary verdict: psfm_chain_step_kernel's body with MB = true, `a.occ` = the frame's kill map.
+// The instantiations live here, under a name of their own: the register census of tests/test_persist_resources.py reads every kernel
+// of psfm_track.hip by (name, template arguments), and that translation unit compiles to what it was.
+// ------------------------------------------------------------------------------------------------
+template <int R, bool OPT>
+__global__ __launch_bounds__(PSFM_CHAIN_BLOCK) PSFM_CHAIN_WAVES void psfm_chain_step_mb_kernel(PsfmChainArgs a)
+{
+    PsfmChainOut o;
+    (void)psfm_chain_step_body<R, OPT, false, true>(a, o);
+}
+
+psfm_status psfm_launch_chain_step_mb(psfm_ctx* c, const PsfmTrackDims& d, const float* flow, const uint8_t* kill, int frame, bool optimize,
+                                      hipStream_t s)
+{
+    PsfmChainArgs a;
+    psfm_fill_chain_args(c, d, flow, kill, frame, a, s);
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    c->prof.kernel_span(PSFM_PROF_CHAIN, &e0, &e1);
+    const dim3 grid((unsigned)((d.cap + PSFM_CHAIN_TILE - 1) / PSFM_CHAIN_TILE)), block(PSFM_CHAIN_BLOCK);
+    if (optimize) {
+        switch (d.ratio) {
+            case 1: hipExtLaunchKernelGGL((psfm_chain_step_mb_kernel<1, true>), grid, block, 0, s, e0, e1, 0, a); break;
+            case 2: hipExtLaunchKernelGGL((psfm_chain_step_mb_kernel<2, true>), grid, block, 0, s, e0, e1, 0, a); break;
+            case 4: hipExtLaunchKernelGGL((psfm_chain_step_mb_kernel<4, true>), grid, block, 0, s, e0, e1, 0, a); break;
+            default: hipExtLaunchKernelGGL((psfm_chain_step_mb_kernel<0, true>), grid, block, 0, s, e0, e1, 0, a); break;
+        }
+    } else {
+        switch (d.ratio) {
+            case 1: hipExtLaunchKernelGGL((psfm_chain_step_mb_kernel<1, false>), grid, block, 0, s, e0, e1, 0, a); break;
+            case 2: hipExtLaunchKernelGGL((psfm_chain_step_mb_kernel<2, false>), grid, block, 0, s, e0, e1, 0, a); break;
+            case 4: hipExtLaunchKernelGGL((psfm_chain_step_mb_kernel<4, false>), grid, block, 0, s, e0, e1, 0, a); break;
+            default: hipExtLaunchKernelGGL((psfm_chain_step_mb_kernel<0, false>), grid, block, 0, s, e0, e1, 0, a); break;
+        }
+    }
+    PSFM_HIP(hipGetLastError());
+    return PSFM_OK;
+}

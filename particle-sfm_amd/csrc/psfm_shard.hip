@@ -43,6 +43,11 @@ extern "C" psfm_status psfm_shard_begin(psfm_ctx* c, int n_flows, int h, int w, 
         psfm_set_error("psfm_shard_begin: bad argument (n_flows=%d h=%d w=%d ratio=%d)", n_flows, h, w, ratio);
         return PSFM_ERR_ARG;
     }
+    if (c->mb_enable) {
+        psfm_set_error("psfm_shard_begin: the context has psfm_ctx_set_motion_boundary on; a track-sharded run does not form the "
+                       "motion-boundary verdict");
+        return PSFM_ERR_ARG;
+    }
     // the ids over ranks come from the key last << 47 | birth << 31 | grid index (psfm_result_keys): 16 bits per time field, 31 for
     // the grid index (a grid has fewer than 2^30 points: psfm_track_dims)
     if (n_flows + 2 >= (1 << PSFM_KEY_TIME_BITS)) {

@@ -33,6 +33,7 @@ EXPORTS = [
     "psfm_database_compact_again",
     "psfm_sparse_depth", "psfm_sparse_depth_sort_ids", "psfm_ctx_set_sparse_depth", "psfm_ctx_get_sparse_depth_budget",
     "psfm_sparse_depth_last_ms", "psfm_colmap_points3d_count", "psfm_colmap_points3d_scan",
+    "psfm_ctx_set_motion_boundary", "psfm_motion_boundary", "psfm_kill_map",
 ]
 
 
@@ -100,6 +101,9 @@ def lib():
     L.psfm_ctx_set_profiling.argtypes = [vp, i32]
     L.psfm_ctx_set_chain_mode.argtypes = [vp, i32]
     L.psfm_ctx_set_solver.argtypes = [vp, i32, i32]
+    L.psfm_ctx_set_motion_boundary.argtypes = [vp, i32, f32]
+    L.psfm_motion_boundary.argtypes = [vp, vp, i32, i32, i32, f32, vp, vp]
+    L.psfm_kill_map.argtypes = [vp, vp, vp, i32, i32, i32, f32, vp, vp]
     L.psfm_solver_counters.argtypes = [vp, ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(ctypes.c_int32)]
     L.psfm_ctx_set_resident_budget.argtypes = [vp, i32]
     L.psfm_resident_capacity.argtypes = [vp, ctypes.POINTER(ctypes.c_int32)]
@@ -193,6 +197,11 @@ class Context:
     def set_chain_mode(self, mode):
         """0 auto (persistent frame loop when the grid fits the device), 1 per-frame launches, 2 persistent loop only."""
         check(lib().psfm_ctx_set_chain_mode(self._h, int(mode)))
+
+    def set_motion_boundary(self, enable, thres=0.02):
+        """Tracks also die on motion boundaries (the reference's commented kill rule, trajectory.py:60): psfm_track / psfm_connect
+        then run one launch per frame; psfm_connect_batch and psfm_shard_begin refuse the context.  Default off."""
+        check(lib().psfm_ctx_set_motion_boundary(self._h, int(bool(enable)), float(thres)))
 
     def set_solver(self, mode, k=0):
         """track_optimize: 0 adaptive (fused solve, launch chain for windows whose solves reject steps), 1 launch chain,

@@ -11,11 +11,13 @@ from .trajectory import run_connect, result_to_trajectory_set, save_track_npy
 
 
 def main_connect_point_trajectories(flow_dir, traj_dir, sample_ratio=2, flow_check_thres=1.0, traj_min_len=3,
-                                    skip_path_consistency=False, skip_exists=False, layout=None, timings=None):
+                                    skip_path_consistency=False, skip_exists=False, layout=None, timings=None, motion_boundary=False):
     """Reference signature (:27) plus `layout`: the pickle state of track.npy -- "reference" (default; the file an
     unmodified particle-sfm checkout, pybind module included, reads) or "csr" (this package's compact arrays;
     PSFM_TRACK_LAYOUT=csr selects it for callers that cannot pass the argument) -- and `timings`: a dict that receives the
-    seconds of the stage's phases (ingest / compute / filter_d2h / write)."""
+    seconds of the stage's phases (ingest / compute / filter_d2h / write) -- and `motion_boundary`: tracks also die
+    on motion boundaries, the kill rule the reference keeps commented out for in-the-wild video (trajectory.py:58-60;
+    PSFM_MOTION_BOUNDARY=1 selects it for callers that cannot pass the argument, e.g. through run_with_psfm.py --motion_boundary)."""
     import time
     import torch
     t0 = time.perf_counter()
@@ -39,7 +41,9 @@ def main_connect_point_trajectories(flow_dir, traj_dir, sample_ratio=2, flow_che
     t1 = time.perf_counter()
     # fwd/bwd checks (utils.py:94-105) + connecting tracks into point trajectories (track.py / track_optimize.py):
     # one call, the occlusion maps stream into the frame loop from a side stream
-    info = run_connect(flows_f, flows_b, flows_f2, flows_b2, flow_check_thres, sample_ratio, return_device=True)
+    motion_boundary = bool(motion_boundary) or os.environ.get("PSFM_MOTION_BOUNDARY", "0") == "1"
+    info = run_connect(flows_f, flows_b, flows_f2, flows_b2, flow_check_thres, sample_ratio, return_device=True,
+                       motion_boundary=motion_boundary)
     if timings is not None:
         torch.cuda.synchronize()
     t2 = time.perf_counter()
@@ -57,7 +61,7 @@ def main_connect_point_trajectories(flow_dir, traj_dir, sample_ratio=2, flow_che
 def main(args):
     main_connect_point_trajectories(args.flow_dir, args.traj_dir, sample_ratio=args.sample_ratio,
                                     flow_check_thres=args.flow_check_thres, traj_min_len=args.traj_min_len,
-                                    skip_path_consistency=args.skip_path_consistency)
+                                    skip_path_consistency=args.skip_path_consistency, motion_boundary=args.motion_boundary)
 
 
 if __name__ == "__main__":
@@ -68,4 +72,5 @@ if __name__ == "__main__":
     parser.add_argument("--traj_min_len", type=int, default=3, help="minimum length of the trajectories")
     parser.add_argument("--flow_check_thres", type=float, default=1.0, help="flow consistency check threshold")
     parser.add_argument("--skip_path_consistency", action='store_true', help='whether to skip the path consistency optimization or not')
+    parser.add_argument("--motion_boundary", action='store_true', help='also end trajectories on motion boundaries (in-the-wild video)')
     main(parser.parse_args())

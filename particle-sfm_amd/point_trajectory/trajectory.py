@@ -31,6 +31,49 @@ def grid_sample(data, xy):
     return out.cpu().numpy()
 
 
+def motion_boundary(flow, thres=0.02):
+    """trajectory.py:39-43: the bool map of pixels whose flow gradient exceeds thres x the flow's norm.  flow: (H,W,2) float32.
+    A device tensor is answered by the device (psfm_motion_boundary, a bool tensor on the same device); anything else by NumPy,
+    operation by operation as the reference evaluates it (every intermediate an f32 array)."""
+    try:
+        import torch
+        on_device = isinstance(flow, torch.Tensor) and flow.is_cuda
+    except ImportError:
+        on_device = False
+    if on_device:
+        ctx = _hip.context(flow.device.index)
+        f = flow.detach().to(torch.float32).contiguous()
+        H, W = int(f.shape[0]), int(f.shape[1])
+        out = torch.empty((H, W), dtype=torch.uint8, device=f.device)
+        _hip.check(_hip.lib().psfm_motion_boundary(ctx.handle, _hip.ptr(f), 1, H, W, float(thres), _hip.ptr(out),
+                                                   _hip.current_stream_ptr(ctx.device)))
+        return out.to(torch.bool)
+    f = np.asarray(flow.detach().cpu().numpy() if hasattr(flow, "detach") else flow)
+    with np.errstate(all="ignore"):
+        dx, dy = np.zeros_like(f), np.zeros_like(f)
+        dx[:, :-1, :] = np.abs(f[:, :-1, :] - f[:, 1:, :])
+        dy[:-1, :, :] = np.abs(f[:-1, :, :] - f[1:, :, :])
+        f_dx, f_dy = np.mean(dx, -1), np.mean(dy, -1)
+        motion = np.sqrt(f_dx ** 2 + f_dy ** 2)
+        return motion > thres * np.linalg.norm(f, ord=2, axis=-1)
+
+
+class _MotionBoundary:
+    """Sets psfm_ctx_set_motion_boundary on a context for the duration of one call (the option is per context, off by default)."""
+
+    def __init__(self, ctx, enable, thres):
+        self.ctx, self.enable, self.thres = ctx, bool(enable), float(thres)
+
+    def __enter__(self):
+        if self.enable:
+            self.ctx.set_motion_boundary(True, self.thres)
+
+    def __exit__(self, *exc):
+        if self.enable:
+            self.ctx.set_motion_boundary(False)
+        return False
+
+
 class TrajectoryList:
     """What track()/track_optimize() return: trajectories in full_trajs order (index == saved id,
     main_connect_point_trajectories.py:56-60), stored as CSR arrays copied once from HBM.
@@ -246,12 +289,16 @@ def _capacity_of(ctx, key):
     return ctx._capacity.get(key, (2.0, 8.0))
 
 
-def run_connect(flows_f, flows_b, flows_f2, flows_b2, thres, sample_ratio, return_device=False):
+def run_connect(flows_f, flows_b, flows_f2, flows_b2, thres, sample_ratio, return_device=False, motion_boundary=False, mb_thres=0.02,
+                ctx=None):
     """flow_check + track / track_optimize in ONE psfm_connect call (the compute part of
     main_connect_point_trajectories.py:36-53): the occlusion maps are produced on a side stream while the frame
-    loop consumes them.  Inputs: (n,H,W,2) float32 device tensors (stride-2 stacks None to skip path consistency)."""
+    loop consumes them.  Inputs: (n,H,W,2) float32 device tensors (stride-2 stacks None to skip path consistency).
+    motion_boundary: tracks also die on motion boundaries of threshold mb_thres (the reference's commented kill rule,
+    trajectory.py:60); ctx: the context that runs the call and keeps the result (default: the calling thread's)."""
     import torch
-    ctx = _hip.context()
+    if ctx is None:
+        ctx = _hip.context()
     n, H, W = int(flows_f.shape[0]), int(flows_f.shape[1]), int(flows_f.shape[2])
     if n < 1:
         raise ValueError("connect: need at least one flow field")
@@ -267,31 +314,39 @@ def run_connect(flows_f, flows_b, flows_f2, flows_b2, thres, sample_ratio, retur
     info = _hip.TrackInfo()
     cap_key = ("connect", n, H, W, int(sample_ratio), f2 is not None)
     lane_f, traj_f = _capacity_of(ctx, cap_key)
-    for attempt in range(6):
-        ctx.set_capacity(lane_f, traj_f)
-        ctx._capacity[cap_key] = (lane_f, traj_f)      # remembered per shape: a sequence that needed larger tables keeps them
-        st = _hip.lib().psfm_connect(ctx.handle, _hip.ptr(flows_f), _hip.ptr(flows_b), _hip.ptr(f2), _hip.ptr(b2), n, H, W,
-                                     float(thres), int(sample_ratio), None, None, ctypes.byref(info),
-                                     _hip.current_stream_ptr(ctx.device))
-        if st != _hip.PSFM_ERR_CAPACITY:
-            break
-        lane_f, traj_f = lane_f * 2.0, traj_f * 4.0
+    with _MotionBoundary(ctx, motion_boundary, mb_thres):
+        for attempt in range(6):
+            ctx.set_capacity(lane_f, traj_f)
+            ctx._capacity[cap_key] = (lane_f, traj_f)      # remembered per shape: a sequence that needed larger tables keeps them
+            st = _hip.lib().psfm_connect(ctx.handle, _hip.ptr(flows_f), _hip.ptr(flows_b), _hip.ptr(f2), _hip.ptr(b2), n, H, W,
+                                         float(thres), int(sample_ratio), None, None, ctypes.byref(info),
+                                         _hip.current_stream_ptr(ctx.device))
+            if st != _hip.PSFM_ERR_CAPACITY:
+                break
+            lane_f, traj_f = lane_f * 2.0, traj_f * 4.0
     _hip.check(st)
     if return_device:
         return info
     return _result_to_host(ctx, info)
 
 
-def run_connect_batch(seqs, thres, sample_ratio):
+def run_connect_batch(seqs, thres, sample_ratio, motion_boundary=False, mb_thres=0.02):
     """psfm_connect_batch: flow_check + track / track_optimize for a BATCH of same-shape sequences (the directory of sequences the
     reference's driver walks, run_particlesfm.py:168-176) with every frame launch covering the whole batch.
     seqs: list of (flows_f, flows_b, flows_f2 | None, flows_b2 | None) device tensors (n_i,H,W,2) -- all with stride-2 stacks or
     none.  Returns (contexts, infos): context i holds sequence i's result (`_result_to_host(ctx, info)`,
-    `result_to_trajectory_set(ctx, info)`) until the calling thread's next batch."""
+    `result_to_trajectory_set(ctx, info)`) until the calling thread's next batch.
+    motion_boundary: the batched launches do not form that verdict (psfm_connect_batch refuses such a context): the sequences then
+    go through run_connect one after the other, each on its own context."""
     import torch
     n_seq = len(seqs)
     if n_seq < 1:
         return [], []
+    if motion_boundary:
+        ctxs = _hip.batch_contexts(n_seq)
+        infos = [run_connect(a, b, a2, b2_, thres, sample_ratio, return_device=True, motion_boundary=True, mb_thres=mb_thres, ctx=c)
+                 for c, (a, b, a2, b2_) in zip(ctxs, seqs)]
+        return ctxs, infos
     H, W = int(seqs[0][0].shape[1]), int(seqs[0][0].shape[2])
     opt = seqs[0][2] is not None
     keep = []           # (tensors created here must outlive the call)
@@ -331,8 +386,9 @@ def run_connect_batch(seqs, thres, sample_ratio):
     return ctxs, [infos[i] for i in range(n_seq)]
 
 
-def run_track(flows, occ_maps, flows_f2, occ_maps_s2, sample_ratio, return_device=False):
-    """Shared driver of track() / track_optimize(): one psfm_track call (whole frame loop on the device)."""
+def run_track(flows, occ_maps, flows_f2, occ_maps_s2, sample_ratio, return_device=False, motion_boundary=False, mb_thres=0.02):
+    """Shared driver of track() / track_optimize(): one psfm_track call (whole frame loop on the device).
+    motion_boundary / mb_thres: as in run_connect."""
     import torch
     ctx = _hip.context()
     fl = _as_device_stack(flows, torch.float32, (1, 1, 2))
@@ -354,16 +410,17 @@ def run_track(flows, occ_maps, flows_f2, occ_maps_s2, sample_ratio, return_devic
     info = _hip.TrackInfo()
     cap_key = ("track", n, H, W, int(sample_ratio), f2 is not None)
     lane_f, traj_f = _capacity_of(ctx, cap_key)
-    for attempt in range(6):
-        ctx.set_capacity(lane_f, traj_f)
-        ctx._capacity[cap_key] = (lane_f, traj_f)
-        st = _hip.lib().psfm_track(ctx.handle, _hip.ptr(fl), _hip.ptr(oc), _hip.ptr(f2), _hip.ptr(o2), n, H, W,
-                                   int(sample_ratio), ctypes.byref(info), _hip.current_stream_ptr(ctx.device))
-        if st != _hip.PSFM_ERR_CAPACITY:
-            break
-        if os.environ.get("PSFM_VERBOSE"):
-            print("psfm_track: %s -> retry with larger tables" % _hip.lib().psfm_last_error().decode(), file=sys.stderr)
-        lane_f, traj_f = lane_f * 2.0, traj_f * 4.0   # tables too small for this sequence: grow and rerun
+    with _MotionBoundary(ctx, motion_boundary, mb_thres):
+        for attempt in range(6):
+            ctx.set_capacity(lane_f, traj_f)
+            ctx._capacity[cap_key] = (lane_f, traj_f)
+            st = _hip.lib().psfm_track(ctx.handle, _hip.ptr(fl), _hip.ptr(oc), _hip.ptr(f2), _hip.ptr(o2), n, H, W,
+                                       int(sample_ratio), ctypes.byref(info), _hip.current_stream_ptr(ctx.device))
+            if st != _hip.PSFM_ERR_CAPACITY:
+                break
+            if os.environ.get("PSFM_VERBOSE"):
+                print("psfm_track: %s -> retry with larger tables" % _hip.lib().psfm_last_error().decode(), file=sys.stderr)
+            lane_f, traj_f = lane_f * 2.0, traj_f * 4.0   # tables too small for this sequence: grow and rerun
     _hip.check(st)
     if return_device:
         return info

@@ -2,7 +2,10 @@
 """Run a script of an unmodified bytedance/particle-sfm checkout with this package's `point_trajectory` in place of
 the checkout's own:
 
-    python /path/to/particle-sfm_amd/run_with_psfm.py [--ref /path/to/particle-sfm] run_particlesfm.py <its arguments>
+    python /path/to/particle-sfm_amd/run_with_psfm.py [--ref /path/to/particle-sfm] [--motion_boundary] run_particlesfm.py <its arguments>
+
+--motion_boundary: trajectories also end on motion boundaries (the kill rule the checkout keeps commented out, trajectory.py:58-60);
+the checkout's script has no such argument, so the switch travels as PSFM_MOTION_BOUNDARY=1.
 
 Why a launcher: `python run_particlesfm.py` puts the checkout's directory at sys.path[0], AHEAD of PYTHONPATH, so
 `from point_trajectory import main_connect_point_trajectories` (run_particlesfm.py:21) would keep resolving to the
@@ -30,8 +33,14 @@ def configure_paths(ref_root):
 
 def main(argv):
     ref = os.environ.get("PSFM_REFERENCE_ROOT", os.getcwd())
-    if len(argv) >= 2 and argv[0] == "--ref":
-        ref, argv = argv[1], argv[2:]
+    while argv and argv[0] in ("--ref", "--motion_boundary"):
+        if argv[0] == "--motion_boundary":
+            os.environ["PSFM_MOTION_BOUNDARY"] = "1"
+            argv = argv[1:]
+        elif len(argv) >= 2:
+            ref, argv = argv[1], argv[2:]
+        else:
+            break
     if not argv:
         sys.exit(__doc__)
     script = argv[0] if os.path.isabs(argv[0]) else os.path.join(ref, argv[0])
