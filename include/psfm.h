@@ -644,7 +644,10 @@ psfm_status psfm_shard_solve_redo_local(psfm_ctx* ctx, const float* flow01, cons
  * area + its 64-byte IPC handle), psfm_shard_peer_open (another process's area), psfm_shard_peer_connect (world <= 8, rank, every rank's
  * area as this process addresses it, every rank's launch size from psfm_shard_solve_blocks; 0 blocks anywhere = PSFM_ERR_ARG: keep the
  * exchange form).  Per frame psfm_shard_solve_peer(frame, epoch) ENQUEUES this rank's launch; all ranks pass the same epoch (a counter
- * they advance together, 1 .. 2^20 - 1, never reused on an area: psfm_shard_peer_epoch).  A launch that gives up (a rank missing, not co-resident) raises the stall flag on every rank --
+ * they advance together, 1 .. 2^20 - 1, never reused on an area: psfm_shard_peer_epoch).  REQUIRED between two psfm_shard_solve_peer calls: a
+ * cross-rank collective (or any point every rank reaches only behind its launch of the solve before) -- consecutive solves reuse the two
+ * sets of leader rows, and a rank that ran ahead into the next solve would overwrite rows another rank's blocks still poll (spurious
+ * give-ups).  psfm_dist.py has the all-reduce of the step marks there.  A launch that gives up (a rank missing, not co-resident) raises the stall flag on every rank --
  * psfm_shard_window_state reports it and the caller redoes that solve with psfm_shard_solve_export / _control. */
 psfm_status psfm_shard_peer_area(psfm_ctx* ctx, void** area_dev, void* ipc_handle_64, void* stream);
 psfm_status psfm_shard_peer_open(psfm_ctx* ctx, const void* ipc_handle_64, int peer_rank, void** mapped);

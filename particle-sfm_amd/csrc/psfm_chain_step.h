@@ -1,6 +1,6 @@
 // psfm_chain_step.h -- the per-frame chain step (K2 + K3: trajectory.py:25-37,45-62 + track.py:38-46 + extend_all :129-152)
 // as a device function, shared by psfm_chain_step_kernel (psfm_track.hip) and the merged frame kernel of track_optimize
-// (psfm_solver.hip: chain step + the whole path-consistency solve of the frame in ONE launch).
+// (psfm_solver_fused.hip: chain step + the whole path-consistency solve of the frame in ONE launch).
 #pragma once
 #include "psfm_internal.h"
 #include "psfm_chain.h"
@@ -107,7 +107,7 @@ void psfm_fill_chain_args(psfm_ctx* c, const PsfmTrackDims& d, const float* flow
                           hipStream_t s);
 void psfm_fill_chain_args_nolaunch(psfm_ctx* c, const PsfmTrackDims& d, const float* flow, const uint8_t* occ, int frame, PsfmChainArgs& a);
 
-// What the merged frame kernel (psfm_solver.hip) takes over from the chain step of a thread's lane: does the lane's track
+// What the merged frame kernel (psfm_solver_fused.hip) takes over from the chain step of a thread's lane: does the lane's track
 // take part in the path-consistency solve of this frame (alive after the step, born at least two frames ago), and its
 // three buffered positions p0 (time frame-1), p1 (the tail, time frame), p2 (= p1 + flow, time frame+1).
 struct PsfmChainOut { bool solve; double2 p0, p1, p2; int tile; };     // tile: first lane of the block's tile

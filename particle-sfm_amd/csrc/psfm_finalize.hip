@@ -596,7 +596,7 @@ psfm_status psfm_finalize(psfm_ctx* c, const PsfmTrackDims& d, hipStream_t s)
                        d.n_flows, d.shift_b, d.shift_d);
     PSFM_HIP(hipGetLastError());
     PsfmCounters* hc = (PsfmCounters*)c->host_pinned;
-    PsfmShard* hs = (PsfmShard*)((char*)c->host_pinned + 512);
+    PsfmShard* hs = psfm_host_shards(c);
     PSFM_HIP(hipMemcpyAsync(hc, ctr, sizeof(PsfmCounters), hipMemcpyDeviceToHost, s));
     PSFM_HIP(hipMemcpyAsync(hs, shards, sizeof(PsfmShard) * PSFM_NSHARD, hipMemcpyDeviceToHost, s));
     PSFM_HIP(hipStreamSynchronize(s));

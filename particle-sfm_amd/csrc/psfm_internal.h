@@ -86,7 +86,7 @@ struct PsfmCounters {
     int abort;        // persistent frame loop: a block gave up (spin limit); every block leaves at its next barrier
     int spill_cnt;    // persistent frame loop: records written to the shared tail behind the private segments
     int sel;          // track_optimize: iterate buffer that holds the accepted positions (times f, f+1) of the last fused
-                      // solve; 0 = they are in the log.  The next chain step copies them on its way (psfm_solver.hip)
+                      // solve; 0 = they are in the log.  The next chain step copies them on its way (psfm_chain_step.h)
     int n_lanes_snap[2]; // n_lanes as the launch in front of frame f left it, in entry f & 1 (set by track_init, by the control
                       // thread of the frame kernel of f-1 and by the solver's write-back): the tile bound every block of the frame
                       // kernel of f agrees on -- n_lanes itself grows while that launch runs, and nothing it reads changes under it
@@ -242,6 +242,10 @@ struct psfm_ctx {
     void* host_pinned = nullptr;  // small pinned staging block
     size_t host_pinned_bytes = 0;
 };
+// ... behind its first 512 bytes (scalar read-backs, each at its user's own offset): finalize's copy of one set of shard tables, then the
+// solver's control block
+static inline PsfmShard* psfm_host_shards(const psfm_ctx* c) { return (PsfmShard*)((char*)c->host_pinned + 512); }
+static inline PsfmSolveCtrl* psfm_host_solve_ctrl(const psfm_ctx* c) { return (PsfmSolveCtrl*)(psfm_host_shards(c) + PSFM_NSHARD); }
 
 // ---- launchers (psfm_track.hip) -------------------------------------------------------------
 psfm_status psfm_launch_flow_check(const float* ff, const float* fb, int n_pairs, int h, int w, float thres,
@@ -289,7 +293,7 @@ void psfm_batch_fill_seq(psfm_ctx* c, const PsfmTrackDims& d, const float* flows
 psfm_status psfm_launch_track_init_batch(const PsfmBatchSeq* tab_dev, int n_seq, int64_t cap_max, hipStream_t s);
 psfm_status psfm_launch_chain_step_batch(psfm_ctx* owner, const PsfmBatchSeq* tab_dev, int n_seq, int ratio, int64_t cap_max, int frame,
                                          bool optimize, hipStream_t s);
-// track_optimize rows (psfm_solver.hip: chain-step arguments + solver parameters of frame 1 + strides) and their launches
+// track_optimize rows (psfm_solver_batch.hip: chain-step arguments + solver parameters of frame 1 + strides) and their launches
 size_t psfm_batch_seq_opt_bytes(void);
 psfm_status psfm_batch_fill_seq_opt(psfm_ctx* c, const PsfmTrackDims& d, const float* flows, const uint8_t* occ, int64_t occ_pitch,
                                     const float* flows_f2, const uint8_t* occ_s2, void* row_host, hipStream_t s);
@@ -330,7 +334,7 @@ psfm_status psfm_sort_pairs32(psfm_ctx* c, unsigned* k_half0, int* v_half0, unsi
 // after psfm_launch_chain_persist; *fallback = true (and PSFM_OK): the loop gave up, rerun with per-frame launches
 psfm_status psfm_finalize_persist(psfm_ctx* c, const PsfmTrackDims& d, bool* fallback, hipStream_t s);
 
-// ---- solver (psfm_solver.hip) ---------------------------------------------------------------
+// ---- solver (psfm_solver.hip: launch chain, resident solve, host driver; fused / frame / device-paced forms: psfm_solver_fused.hip) ----
 // In-place solve on the trajectory log for frame index f (positions at f-1, f, f+1): enqueue `unroll`
 // iterations without host synchronisation / resume a solve that raised the stall flag.
 psfm_status psfm_solve_frame_enqueue(psfm_ctx* c, const PsfmTrackDims& d, const float* flow01, const float* flow12,

@@ -65,7 +65,7 @@ PC_HD double pc_slot_candidate(const PcSlot& T, double a, double b, double xp[4]
     return v[SUM_STEP2];
 }
 
-// iteration 0 has produced the track's constants, start values and the system there (PcInit of psfm_solver.hip): into the slot
+// iteration 0 has produced the track's constants, start values and the system there (PcInit of psfm_pc_tracks.h): into the slot
 PC_HD void pc_slot_fill(PcSlot& T, double s, const PcConst& c, const double x[4], const PcSys& y)
 {
     T.s = s; T.S0q = c.S0q; T.S1q = c.S1q;

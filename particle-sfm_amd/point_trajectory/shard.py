@@ -10,7 +10,7 @@ import numpy as np
 
 from . import _hip
 
-SUM_GMAX, N_SUM, K_MAX = 5, 13, 8          # csrc/psfm_solver.hip: slot combined by max, sums per iteration, fused iterations
+SUM_GMAX, N_SUM, K_MAX = 5, 13, 8          # csrc/psfm_pc_core.h, psfm_pc_params.h: slot combined by max, sums per iteration, fused iterations
 
 
 class HipShardEngine:

@@ -352,7 +352,7 @@ def connect_sharded(engine, flows_f, flows_b, flows_f2, flows_b2, thres, sample_
     if hasattr(engine, "set_local"):     # one rank: nothing of a solve is exchanged -- rejecting solves take the one-GPU call's forms
         engine.set_local(world == 1)
     # A rank whose lane / record tables run full learns it when it finalizes (PSFM_ERR_CAPACITY from psfm_shard_finish: the launches behind
-    # an overflow are harmless by themselves, csrc/psfm_solver.hip clamps what they count on).  That is behind the last collective of the
+    # an overflow are harmless by themselves, csrc/psfm_solver_fused.hip clamps what they count on).  That is behind the last collective of the
     # recurrence, so the ranks can agree on it: every rank reports, and if ANY table was too small ALL of them run Stage B again with
     # the tables doubled / quadrupled -- what run_connect does for the one-GPU call (trajectory.py), collectively.
     for attempt in range(6):

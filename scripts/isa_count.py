@@ -2,7 +2,7 @@
 """Static instruction census of one kernel in a hipcc -S listing: per basic block, how many VALU / SALU / VMEM / LDS
 instructions, and which VALU mnemonics dominate.  Used to see what the solver's iteration loop is made of without a GPU.
 
-    hipcc --offload-arch=gfx950 -O3 ... -S --cuda-device-only -o solver.s csrc/psfm_solver.hip
+    hipcc --offload-arch=gfx950 -O3 ... -S --cuda-device-only -o solver.s csrc/psfm_solver_fused.hip
     python scripts/isa_count.py solver.s _Z20psfm_pc_fused_kernelILi3EEv8PcParams [min_block_size]
 """
 import collections

@@ -1,5 +1,5 @@
 """Map of one kernel in a hipcc -S listing: labels, branches, barriers, sleeps, scratch (spill) traffic and VMEM, with line offsets.
-    hipcc ... -S --cuda-device-only csrc/psfm_solver.hip -o /tmp/solver.s ; python scripts/isa_map.py /tmp/solver.s <mangled-prefix>"""
+    hipcc ... -S --cuda-device-only csrc/psfm_solver.hip (or psfm_solver_fused.hip / _batch.hip: the unit that defines the kernel) -o /tmp/solver.s ; python scripts/isa_map.py /tmp/solver.s <mangled-prefix>"""
 import sys
 L = open(sys.argv[1]).read().split('\n')
 pref = sys.argv[2]

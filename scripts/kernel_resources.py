@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-kernel register / LDS / occupancy table of one csrc/*.hip TU (hipcc -Rpass-analysis=kernel-resource-usage).
 
-    python scripts/kernel_resources.py psfm_solver.hip [extra hipcc flags]
+    python scripts/kernel_resources.py psfm_solver_fused.hip [extra hipcc flags]
 """
 import os
 import re

@@ -69,7 +69,7 @@ struct HostTrack { int birth, gidx; std::vector<double2> pts; int last; };
 // time, birth frame, birth grid index), psfm_key); points into xy (cap_points x 2).
 // flows2 / occs2 != NULL: track_optimize.py:24-53 -- behind the step of frame t >= 1 the tracks with three buffered points
 // (times t-1, t, t+1) are optimised together (trajectory.py:161-194): references and weight from the fp32 sampler at p0
-// (restating pc_init_tracks of psfm_solver.hip with the device's sampler), the solve by the device's launch chain.
+// (restating pc_init_tracks of psfm_pc_tracks.h with the device's sampler), the solve by the device's launch chain.
 // iters_out (n_flows - 1 entries, may be NULL): iterations of every solve.
 extern "C" long psfm_host_track(const float* const* flows, const uint8_t* const* occs, int n_flows, int H, int W, int ratio,
                                 int* birth_out, int* len_out, double* xy_out, long cap_tracks, long cap_points, long* n_points_out,

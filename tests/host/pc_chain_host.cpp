@@ -3,7 +3,7 @@
 // psfm_pc_iter_kernel / psfm_pc_persist_kernel run it -- iteration 0, then per round either the evaluate-ahead form
 // (candidate of the step the control block names, its cost, the system there) or the refresh form (the system at x for a
 // raised mu), the 13 sums of a round added in track order, pc_chain_control on them.  The loop bodies below restate
-// pc_init_tracks / pc_iter_tracks of psfm_solver.hip line by line; everything they call is the device's own code.
+// pc_init_tracks / pc_iter_tracks of psfm_pc_tracks.h line by line; everything they call is the device's own code.
 // Test infrastructure (compiled by the test with g++ -O2 -mfma -ffp-contract=off).
 #include <vector>
 
@@ -94,7 +94,7 @@ extern "C" int pc_host_chain_solve(long n, const double* x0, const double* ref1,
     return pc_host_chain_solve_ex(n, x0, ref1, ref2, scale, flow, H, W, pair, 0, x_out, stats, costs);
 }
 
-// ---- the FUSED solve (psfm_pc_fused_kernel / the frame kernels: pc_fused_body + pc_fused_replay of psfm_solver.hip) ----
+// ---- the FUSED solve (psfm_pc_fused_kernel / the frame kernels: pc_fused_body + pc_fused_replay of psfm_pc_fused.h) ----
 // K trust-region iterations per track speculated as accepted Gauss-Newton steps at mu = min_mu, the K x 13 sums replayed by
 // pc_control_step; when all K were accepted without ending the solve, continuation launches of up to two more iterations from
 // the last iterate (pc_more_body); the first decision that is not "Gauss-Newton step accepted" ends the belief.
