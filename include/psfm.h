@@ -217,6 +217,19 @@ psfm_status psfm_path_consistency_eval(psfm_ctx* ctx, const double* uv12, const 
  * on their records (csrc/psfm_sort.hip); exported so that the sort can be checked on its own.  n < 2^31.  Asynchronous on `stream`. */
 psfm_status psfm_sort_records(psfm_ctx* ctx, uint32_t* keys, int32_t* values, int64_t n, int end_bit, void* stream);
 
+/* The same for keys of up to 64 bits, 1 <= end_bit <= 64 (the 8-byte instances of the same kernels: what the id assignment runs for
+ * long or dense sequences and for batches whose sequence number does not fit beside a 32-bit key): ceil(end_bit / 8) passes, the bits
+ * at and above end_bit order nothing and the keys leave whole.  STABLE; in place; n < 2^31.  Asynchronous on `stream`. */
+psfm_status psfm_sort_records64(psfm_ctx* ctx, uint64_t* keys, int32_t* values, int64_t n, int end_bit, void* stream);
+
+/* Which forms the LAST id assignment of this context ran (psfm_track / psfm_connect; for psfm_connect_batch: the context that owns the
+ * batch, ctxs[0]) -- they give the same bytes, so nothing else tells them apart.
+ *   sort_form     0 none yet, 1 this library's sort on 32-bit keys, 2 this library's sort on 64-bit keys, 3 rocPRIM's device sort
+ *   offsets_form  0 none yet, 1 one-block group plan, 3 decode + scan over the trajectories (more than 16 384 (death, birth) groups:
+ *                 n_flows > 178); 2 is kept for a chunked group plan, which was measured slower than 3 and is not built in
+ * Reads host-side state only; either pointer may be NULL. */
+psfm_status psfm_ctx_get_finalize_forms(psfm_ctx* ctx, int* sort_form, int* offsets_form);
+
 /* track.py:24-50 when flows_f2 == NULL, track_optimize.py:24-53 otherwise.
  *   flows    (n_flows,H,W,2) f32      occ     (n_flows,H,W) u8
  *   flows_f2 (n_flows-1,H,W,2) f32    occ_s2  (n_flows-1,H,W) u8        (stride-2 stacks)

@@ -370,6 +370,39 @@ extern "C" psfm_status psfm_sort_records(psfm_ctx* c, uint32_t* keys, int32_t* v
     return PSFM_OK;
 }
 
+extern "C" psfm_status psfm_sort_records64(psfm_ctx* c, uint64_t* keys, int32_t* values, int64_t n, int end_bit, void* stream)
+{
+    PSFM_CHECK_CTX(c);
+    PsfmGate gate(c->device, 0);
+    if (n < 0 || n >= (1ll << 31) || end_bit < 1 || end_bit > 64 || (n > 0 && (!keys || !values))) {
+        psfm_set_error("psfm_sort_records64: bad argument (n=%lld end_bit=%d)", (long long)n, end_bit);
+        return PSFM_ERR_ARG;
+    }
+    if (n == 0) return PSFM_OK;
+    hipStream_t s = (hipStream_t)stream;
+    psfm_status st;
+    // (staged through the context's sort buffers, as psfm_sort_records does)
+    if ((st = c->sort_keys.ensure(sizeof(unsigned long long) * (size_t)n * 2)) != PSFM_OK) return st;
+    if ((st = c->sort_lanes.ensure(sizeof(int) * (size_t)n * 2)) != PSFM_OK) return st;
+    const int64_t half = psfm_sort_pairs64_passes((unsigned)end_bit) % 2 == 0 ? 0 : n;
+    unsigned long long* k0 = c->sort_keys.as<unsigned long long>();
+    int* v0 = c->sort_lanes.as<int>();
+    PSFM_HIP(hipMemcpyAsync(k0 + half, keys, sizeof(unsigned long long) * (size_t)n, hipMemcpyDeviceToDevice, s));
+    PSFM_HIP(hipMemcpyAsync(v0 + half, values, sizeof(int) * (size_t)n, hipMemcpyDeviceToDevice, s));
+    if ((st = psfm_sort_pairs64(c, k0, v0, k0 + n, v0 + n, n, (unsigned)end_bit, s)) != PSFM_OK) return st;
+    PSFM_HIP(hipMemcpyAsync(keys, k0, sizeof(unsigned long long) * (size_t)n, hipMemcpyDeviceToDevice, s));
+    PSFM_HIP(hipMemcpyAsync(values, v0, sizeof(int) * (size_t)n, hipMemcpyDeviceToDevice, s));
+    return PSFM_OK;
+}
+
+extern "C" psfm_status psfm_ctx_get_finalize_forms(psfm_ctx* c, int* sort_form, int* offsets_form)
+{
+    PSFM_CHECK_CTX(c);
+    if (sort_form) *sort_form = c->fin_sort_form;
+    if (offsets_form) *offsets_form = c->fin_offsets_form;
+    return PSFM_OK;
+}
+
 // Sizes of one run of the frame recurrence.  g_own < 0: the whole stride-r grid; otherwise the number of grid points whose
 // births this process owns (track-sharded runs): lane / record tables are sized for those, keys for the whole grid.
 psfm_status psfm_track_dims(psfm_ctx* c, int n_flows, int h, int w, int ratio, int64_t g_own, PsfmTrackDims& d)

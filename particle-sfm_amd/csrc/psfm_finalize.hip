@@ -6,7 +6,8 @@
 //     id = rank under the key (last_valid_time, birth_frame, birth_grid_index)
 // and the saved id is that rank (main_connect_point_trajectories.py:56-60).  The frame loop recorded one
 // (key, lane) pair per finished track; here the survivors are appended, the pairs are radix-sorted by
-// key (rocPRIM device radix sort on the used key bits only), lengths are scanned into offsets, and the
+// key (on the used key bits only: psfm_sort.hip / psfm_sort64.hip, rocPRIM's device sort for 64-bit keys of
+// more than PSFM_SORT64_MAX_N records and behind PSFM_FIN_SORT=0), lengths are scanned into offsets, and the
 // frame-major log is transposed into a track-major (n_points,2) f64 array through LDS tiles so that
 // both the slab reads (consecutive lanes) and the result writes (consecutive times) are coalesced.
 #include <cstring>
@@ -142,7 +143,10 @@ __global__ __launch_bounds__(PSFM_BLOCK) void psfm_decode32_kernel(const unsigne
 // group starts, ONE block turns the (n_flows + 2)(n_flows + 3) / 2 starts into counts and offsets, and the gather computes birth /
 // length / offset of its 64 trajectories from their keys (and stores them for psfm_result_*).  That replaces the decode kernel and a
 // three-kernel scan over n + 1 int64 (2 M entries at the headline shape: 45 us of launches for what 5 253 groups say).  Sequences
-// with more groups than the plan block holds in LDS (n_flows > 178) keep the decode + scan form.
+// with more groups than the plan block holds in LDS (n_flows > 178) keep the decode + scan form.  (Measured and kept out: the same
+// plan swept over chunks of 16 384 groups by one block, counts back to front and offsets front to back with the carries across the
+// chunk edges -- 81 k groups at 1080p x 401 frames cost 55 us more than decode + scan over 6.9 M trajectories, 502 k groups at
+// 480 x 640 x 1000 frames 720 us more than over 10.7 M: profiles/EXPERIMENTS.md 20.)
 #define PSFM_PLAN_MAX_GROUPS 16384
 #define PSFM_PLAN_BLOCK 1024
 struct PsfmPlan {
@@ -485,18 +489,27 @@ static PsfmKeyFmt psfm_key_fmt(const PsfmTrackDims& d, unsigned* end_bit)
     return f;
 }
 
-// Which half of sort_keys / sort_lanes the compaction fills: the second (rocPRIM sorts second half -> first half), unless this file's
-// own sort runs an even number of passes -- it ping-pongs between the halves and has to END in the first.
+// Which half of sort_keys / sort_lanes the compaction fills: the second (rocPRIM sorts second half -> first half), unless this
+// library's own sort (psfm_sort.hip, 32- or 64-bit keys) runs an even number of passes -- it ping-pongs between the halves and has to
+// END in the first.
+// 64-bit keys: the own sort up to PSFM_SORT64_MAX_N records, rocPRIM's above -- inside the finalize the own sort wins where the sort is
+// bound by its launches and loses where it is bound by bandwidth (its scatter kernel holds two blocks per CU: 53 KB of LDS each);
+// figures by record count in profiles/EXPERIMENTS.md 20.
+#define PSFM_SORT64_MAX_N 5000000ll
 static bool psfm_own_sort(const PsfmKeyFmt& fmt, int64_t n)
 {
-    static const int on = getenv("PSFM_FIN_SORT") ? atoi(getenv("PSFM_FIN_SORT")) : 1;      // 0: rocPRIM's device sort (A/B, tests)
-    return on && fmt.use32 && n < (1ll << 31);
+    static const int on = getenv("PSFM_FIN_SORT") ? atoi(getenv("PSFM_FIN_SORT")) : 1;      // 0: rocPRIM's device sort; 2: the own sort at any size (A/B, tests)
+    return on && n < (1ll << 31) && (fmt.use32 || on == 2 || n <= PSFM_SORT64_MAX_N);
+}
+static int psfm_own_sort_passes(const PsfmKeyFmt& fmt, unsigned end_bit)
+{
+    return fmt.use32 ? psfm_sort_pairs32_passes(end_bit) : psfm_sort_pairs64_passes(end_bit);
 }
 static bool psfm_records_in_first_half(const PsfmTrackDims& d, int64_t n)
 {
     unsigned end_bit = 0;
     const PsfmKeyFmt fmt = psfm_key_fmt(d, &end_bit);
-    return psfm_own_sort(fmt, n) && (psfm_sort_pairs32_passes(end_bit) % 2 == 0);
+    return psfm_own_sort(fmt, n) && (psfm_own_sort_passes(fmt, end_bit) % 2 == 0);
 }
 
 // common tail: (key, lane) records already compacted into the halves of sort_keys / sort_lanes psfm_records_in_first_half() names
@@ -511,21 +524,27 @@ static psfm_status psfm_finalize_sorted(psfm_ctx* c, const PsfmTrackDims& d, int
     size_t tmp_bytes = 0, scan_bytes = 0;
     PSFM_HIP(rocprim::exclusive_scan(nullptr, scan_bytes, (int64_t*)nullptr, (int64_t*)nullptr, (int64_t)0,
                                      (size_t)(n + 1), rocprim::plus<int64_t>(), s));
+    c->fin_sort_form = 0; c->fin_offsets_form = 0;
     if (psfm_own_sort(fmt, n)) {
         if ((st = c->sort_tmp.ensure(scan_bytes)) != PSFM_OK) return st;      // (before the sort's launches: growing the buffer frees it)
-        if ((st = psfm_sort_pairs32(c, c->sort_keys.as<unsigned>(), l_out, c->sort_keys.as<unsigned>() + n, l_in, n, end_bit, s)) != PSFM_OK) return st;
+        if (fmt.use32) st = psfm_sort_pairs32(c, c->sort_keys.as<unsigned>(), l_out, c->sort_keys.as<unsigned>() + n, l_in, n, end_bit, s);
+        else st = psfm_sort_pairs64(c, c->sort_keys.as<unsigned long long>(), l_out, c->sort_keys.as<unsigned long long>() + n, l_in, n, end_bit, s);
+        if (st != PSFM_OK) return st;
+        c->fin_sort_form = fmt.use32 ? 1 : 2;
     } else if (fmt.use32) {
         unsigned* k_in = c->sort_keys.as<unsigned>() + n;
         unsigned* k_out = c->sort_keys.as<unsigned>();
         PSFM_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, k_in, k_out, l_in, l_out, (size_t)n, 0u, end_bit, s));
         if ((st = c->sort_tmp.ensure(tmp_bytes > scan_bytes ? tmp_bytes : scan_bytes)) != PSFM_OK) return st;
         PSFM_HIP(rocprim::radix_sort_pairs(c->sort_tmp.p, tmp_bytes, k_in, k_out, l_in, l_out, (size_t)n, 0u, end_bit, s));
+        c->fin_sort_form = 3;
     } else {
         unsigned long long* k_in = c->sort_keys.as<unsigned long long>() + n;
         unsigned long long* k_out = c->sort_keys.as<unsigned long long>();
         PSFM_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, k_in, k_out, l_in, l_out, (size_t)n, 0u, end_bit, s));
         if ((st = c->sort_tmp.ensure(tmp_bytes > scan_bytes ? tmp_bytes : scan_bytes)) != PSFM_OK) return st;
         PSFM_HIP(rocprim::radix_sort_pairs(c->sort_tmp.p, tmp_bytes, k_in, k_out, l_in, l_out, (size_t)n, 0u, end_bit, s));
+        c->fin_sort_form = 3;
     }
     // birth / length / offset of every trajectory: from the group plan (few groups), else decode + scan over the trajectories
     if ((st = c->res_birth.ensure(sizeof(int) * n)) != PSFM_OK) return st;
@@ -554,8 +573,10 @@ static psfm_status psfm_finalize_sorted(psfm_ctx* c, const PsfmTrackDims& d, int
                            c->res_off.as<int64_t>() + n);
         PSFM_HIP(hipGetLastError());
         c->fin_marks_clean = true;
+        c->fin_offsets_form = 1;
         pl.gstart = gstart; pl.goff = goff;
     } else {
+        c->fin_offsets_form = 3;
         if ((st = c->scan_tmp.ensure(sizeof(int64_t) * (n + 1))) != PSFM_OK) return st;
         if (fmt.use32)
             hipLaunchKernelGGL(psfm_decode32_kernel, dim3((unsigned)((n + 1 + PSFM_BLOCK - 1) / PSFM_BLOCK)), dim3(PSFM_BLOCK), 0, s,
@@ -928,7 +949,7 @@ psfm_status psfm_finalize_batch(psfm_ctx* own, psfm_ctx* const* ctxs, const Psfm
     if ((st = own->scan_tmp.ensure(sizeof(int64_t) * (size_t)(N + 1) * 2)) != PSFM_OK) return st;
     // (this file's sort ends in the first half whatever its pass count: with an even count the records start there)
     const bool own_sort = psfm_own_sort(fmt, N);
-    const int64_t half = (own_sort && psfm_sort_pairs32_passes(sort_end) % 2 == 0) ? 0 : N;
+    const int64_t half = (own_sort && psfm_own_sort_passes(fmt, sort_end) % 2 == 0) ? 0 : N;
     unsigned long long* kdst = fmt.use32 ? (unsigned long long*)(own->sort_keys.as<unsigned>() + half) : own->sort_keys.as<unsigned long long>() + half;
     hipLaunchKernelGGL(psfm_compact_shards_batch_kernel, dim3(8, PSFM_NSHARD, (unsigned)n_seq), dim3(PSFM_BLOCK), 0, s, dT, kdst,
                        own->sort_lanes.as<int>() + half, fmt, seq_shift);
@@ -938,9 +959,13 @@ psfm_status psfm_finalize_batch(psfm_ctx* own, psfm_ctx* const* ctxs, const Psfm
     size_t tmp_bytes = 0, scan_bytes = 0;
     PSFM_HIP(rocprim::exclusive_scan(nullptr, scan_bytes, (int64_t*)nullptr, (int64_t*)nullptr, (int64_t)0, (size_t)(N + 1),
                                      rocprim::plus<int64_t>(), s));
+    own->fin_sort_form = 0; own->fin_offsets_form = 0;
     if (own_sort) {
         if ((st = own->sort_tmp.ensure(scan_bytes)) != PSFM_OK) return st;      // (before the sort's launches: growing the buffer frees it)
-        if ((st = psfm_sort_pairs32(own, own->sort_keys.as<unsigned>(), l_out, own->sort_keys.as<unsigned>() + N, l_in, N, sort_end, s)) != PSFM_OK) return st;
+        if (fmt.use32) st = psfm_sort_pairs32(own, own->sort_keys.as<unsigned>(), l_out, own->sort_keys.as<unsigned>() + N, l_in, N, sort_end, s);
+        else st = psfm_sort_pairs64(own, own->sort_keys.as<unsigned long long>(), l_out, own->sort_keys.as<unsigned long long>() + N, l_in, N, sort_end, s);
+        if (st != PSFM_OK) return st;
+        own->fin_sort_form = fmt.use32 ? 1 : 2;
     } else if (fmt.use32) {
         unsigned* k_in = own->sort_keys.as<unsigned>() + N;
         unsigned* k_out = own->sort_keys.as<unsigned>();
@@ -954,6 +979,8 @@ psfm_status psfm_finalize_batch(psfm_ctx* own, psfm_ctx* const* ctxs, const Psfm
         if ((st = own->sort_tmp.ensure(tmp_bytes > scan_bytes ? tmp_bytes : scan_bytes)) != PSFM_OK) return st;
         PSFM_HIP(rocprim::radix_sort_pairs(own->sort_tmp.p, tmp_bytes, k_in, k_out, l_in, l_out, (size_t)N, 0u, sort_end, s));
     }
+    if (!own_sort) own->fin_sort_form = 3;
+    own->fin_offsets_form = 3;
     // 4. decode -> per-sequence birth / length, combined lengths -> ONE scan -> per-sequence offsets; 5. the transpose gather
     int64_t* len64 = own->scan_tmp.as<int64_t>();
     int64_t* scan = len64 + (N + 1);

@@ -25,6 +25,10 @@
 // Tiles are read "wave-striped" (wave w, round i, lane l <-> element 1024 w + 64 i + l), so the order (wave, round, lane)
 // in which a digit's elements are ranked IS their order in memory: every pass is stable, which is what LSD needs.
 // 506 tiles at the headline shape: two resident blocks per CU in S, no look-back chain, no device-wide ordering between tiles.
+//
+// Keys wider than 32 bits (long or dense sequences, batches whose sequence number does not fit beside a 32-bit key, COLMAP ids) are
+// sorted by the sibling kernels of psfm_sort64.hip -- the same structure on 8-byte keys, in a translation unit of its own so that the
+// kernels below, which the headline runs, stay the code they were.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>

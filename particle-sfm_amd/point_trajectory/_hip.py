@@ -23,7 +23,7 @@ EXPORTS = [
     "psfm_shard_solve_writeback", "psfm_shard_solve_record", "psfm_shard_finish", "psfm_result_keys",
     "psfm_shard_solve_control_async", "psfm_shard_window_state", "psfm_shard_peek_stall", "psfm_shard_frame",
     "psfm_shard_solve_control_chain_async", "psfm_shard_solve_poll", "psfm_shard_solve_local", "psfm_shard_solve_redo_local", "psfm_connect_batch", "psfm_solver_launches", "psfm_ctx_set_resident_budget", "psfm_resident_capacity", "psfm_load_flo_stack",
-    "psfm_path_consistency_eval", "psfm_sort_records",
+    "psfm_path_consistency_eval", "psfm_sort_records", "psfm_sort_records64", "psfm_ctx_get_finalize_forms",
     "psfm_shard_peer_area", "psfm_shard_peer_epoch", "psfm_shard_peer_open", "psfm_shard_peer_connect", "psfm_shard_solve_blocks", "psfm_shard_solve_peer",
     "psfm_labels_begin", "psfm_labels_merge_window", "psfm_labels_finish", "psfm_labels_device", "psfm_labels_copy", "psfm_labels_to_matches",
     "psfm_traj_augment", "psfm_traj_encode_weight_count", "psfm_traj_encode",
@@ -91,6 +91,8 @@ def lib():
     L.psfm_optimize_location.argtypes = [vp, vp, vp, vp, vp, vp, i64, i32, i32, vp, ctypes.POINTER(SolveStats), vp]
     L.psfm_path_consistency_eval.argtypes = [vp, vp, vp, vp, vp, vp, i64, i32, i32, vp, vp, vp]
     L.psfm_sort_records.argtypes = [vp, vp, vp, i64, i32, vp]
+    L.psfm_sort_records64.argtypes = [vp, vp, vp, i64, i32, vp]
+    L.psfm_ctx_get_finalize_forms.argtypes = [vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]
     L.psfm_track.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, ctypes.POINTER(TrackInfo), vp]
     L.psfm_connect.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, vp, vp, ctypes.POINTER(TrackInfo), vp]
     L.psfm_connect_batch.argtypes = [ctypes.POINTER(vp), i32, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp),
@@ -228,6 +230,14 @@ class Context:
         check(lib().psfm_solver_launches(self._h, ctypes.byref(r), ctypes.byref(g), ctypes.byref(it)))
         out.update({"resident_launches": r.value, "resident_giveups": g.value, "iteration_launches": it.value})
         return out
+
+    def finalize_forms(self):
+        """Which forms the last id assignment of this context ran (for a batch: the context that owns it).  sort: 0 none yet, 1 the
+        library's sort on 32-bit keys, 2 on 64-bit keys, 3 rocPRIM; offsets: 0 none yet, 1 one-block group plan, 3 decode + scan
+        (2: a chunked group plan, not built in)."""
+        a, b = ctypes.c_int32(), ctypes.c_int32()
+        check(lib().psfm_ctx_get_finalize_forms(self._h, ctypes.byref(a), ctypes.byref(b)))
+        return {"sort": int(a.value), "offsets": int(b.value)}
 
     def set_sparse_depth(self, budget_bytes=1 << 30, timing=False):
         """psfm_sfm.convert: bytes of depth maps + winner maps (12 per pixel) one psfm_sparse_depth call may take (0: no limit; one

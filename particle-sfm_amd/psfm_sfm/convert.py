@@ -257,11 +257,30 @@ def sort_ids_device(ctx, ids_dev):
     return srt, row
 
 
+def sort_ids_device64(ctx, ids_dev):
+    """ids (device i64, all in [0, 2^63)) -> (sorted ids i64, rows i32) through the library's 64-bit record sort
+    (psfm_sort_records64 over the bit length of the largest id).  A negative id is a ValueError."""
+    import torch
+    from point_trajectory import _hip
+    n = ids_dev.numel()
+    if n == 0:
+        return ids_dev.clone(), torch.empty(0, dtype=torch.int32, device=ids_dev.device)
+    lo, hi = int(ids_dev.min()), int(ids_dev.max())
+    if lo < 0:
+        raise ValueError("sort_ids_device64 needs every id in [0, 2^63): got %d" % lo)
+    srt = ids_dev.contiguous().clone()                      # (sorted in place; as u64 keys an id in [0, 2^63) is its own value)
+    row = torch.arange(n, dtype=torch.int32, device=ids_dev.device)
+    _hip.check(_hip.lib().psfm_sort_records64(ctx.handle, _hip.ptr(srt), _hip.ptr(row), n, max(1, hi.bit_length()),
+                                              _hip.current_stream_ptr(ctx.device)))
+    return srt, row
+
+
 def sparse_depth_device(model, ctx=None, sort="auto"):
     """Yields (image name, depth (h, w) f64 torch tensor on the device) batch by batch; a batch is as many consecutive images as the
     context's budget admits (Context.set_sparse_depth; 12 bytes per pixel).  sort: "device" (ids below 2^32: the library's record
-    sort), "host" (np.argsort, any id), "auto" (device when every id is below 2^32).  An observation whose id names no point raises
-    KeyError(the smallest such id of the batch), as the reference's dict lookup does; the context stays usable."""
+    sort), "device64" (ids below 2^63: its 64-bit record sort), "host" (np.argsort, any id), "auto" (device when every id is below
+    2^32, else host).  An observation whose id names no point raises KeyError(the smallest such id of the batch), as the reference's
+    dict lookup does; the context stays usable."""
     import ctypes
     import torch
     from point_trajectory import _hip
@@ -278,11 +297,15 @@ def sparse_depth_device(model, ctx=None, sort="auto"):
         if not small:
             raise ValueError("sort='device' needs every point3D id in [0, 2^32)")
         srt, row = sort_ids_device(ctx, torch.from_numpy(np.ascontiguousarray(model.ids)).to(dev))
+    elif sort == "device64":
+        if n_pts and int(model.ids.min()) < 0:
+            raise ValueError("sort='device64' needs every point3D id in [0, 2^63)")
+        srt, row = sort_ids_device64(ctx, torch.from_numpy(np.ascontiguousarray(model.ids, np.int64)).to(dev))
     elif sort == "host":
         order = np.argsort(model.ids, kind="stable")
         srt, row = torch.from_numpy(model.ids[order]).to(dev), torch.from_numpy(order.astype(np.int32)).to(dev)
     else:
-        raise ValueError("sort must be 'auto', 'device' or 'host'")
+        raise ValueError("sort must be 'auto', 'device', 'device64' or 'host'")
     xyz = torch.from_numpy(np.ascontiguousarray(model.xyz, np.float64)).to(dev)
     xys = torch.from_numpy(np.ascontiguousarray(model.xys, np.float64)).to(dev)
     ids = torch.from_numpy(np.ascontiguousarray(model.point3D_ids, np.int64)).to(dev)
