@@ -562,6 +562,38 @@ psfm_status psfm_colmap_points3d_count(const void* buf, uint64_t nbytes, uint64_
 psfm_status psfm_colmap_points3d_scan(const void* buf, uint64_t nbytes, uint64_t* ids_out, double* xyz_out, double* err_out,
                                       uint64_t* track_len_out);
 
+/* sfm/convert.py:26-41 and :95 (normalize_depth_for_display, gray2rgb, plt.imsave's byte conversion): the display images of the sparse
+ * depth maps of one psfm_sparse_depth call (csrc/psfm_depth_display.hip; the per-element rules are csrc/psfm_depth_display.h).
+ * psfm_depth_display         depth: DEVICE, what psfm_sparse_depth wrote (sum of h * w f64, 16-byte aligned).  img_desc_host: the
+ *                            SAME 64-byte descriptors on the HOST (no smaller one is defined: a caller has them already); only w, h
+ *                            and out_off are read, the maps follow each other without gaps, the first at 0.  pc in [0, 100] (the
+ *                            reference: 98).  table_host 256 x 4 u8 and bad_rgba_host 4 u8 on the HOST: the colour map at 0..255
+ *                            and at NaN as RGBA bytes (data: matplotlib's map times 255, truncated, alpha 255).  rgba_out: DEVICE,
+ *                            16-byte aligned, 4 bytes per pixel at the same element offsets as depth.  Per image:
+ *                              valid   d > 0, n of them; n = 0: no image, its part of rgba_out is left untouched
+ *                              inv     1.0 / (d + 1.0) for every pixel: one f64 add, one IEEE division (d = -1 gives +inf)
+ *                              z1, z2  np.percentile (method 'linear') of the valid inv at pc and at 100 - pc: vi = (n - 1) * (q / 100),
+ *                                      j = floor(vi), g = vi - j, a = s[j], b = s[min(j + 1, n - 1)], a + (b - a) * g, and where
+ *                                      g >= 0.5: b - (b - a) * (1 - g); every operation rounded once.  The order statistics come
+ *                                      from an MSB-first 8-bit radix select over the bit patterns (integer atomics only: identical
+ *                                      bytes from identical calls)
+ *                              pixel   v = (inv - z2) / (z1 - z2) clamped to [0, 1] (NaN stays NaN), v32 = (float)v, xa = v32 * 256.0f,
+ *                                      index 255 where xa == 256 else xa truncated; bytes = table[index], NaN: the bad entry
+ *                            n_valid_out (n_img) i64 and z_out (n_img, 2) f64 (z1, z2; 0.0 for n = 0): HOST, either may be NULL.
+ *                            Synchronises `stream` (once in the middle too: the counts size the workspace).  19 launches whatever
+ *                            n_img.  PSFM_ERR_ARG, nothing launched, the context stays usable: a NULL argument, n_img < 1, w or
+ *                            h < 1, an image of 2^31 pixels or more, descriptors that overlap or leave gaps, pc not finite or outside
+ *                            [0, 100], a pointer that is not 16-byte aligned.  depth must not change during the call.
+ * psfm_ctx_set_depth_display timing != 0: events around the count, compact, select and colour passes of every call, read by
+ *                            psfm_depth_display_last_ms (ms4[0..3], milliseconds).
+ * psfm_depth_display_chunk   valid pixels one block of the compaction covers at most (tests place maps around it). */
+psfm_status psfm_depth_display(psfm_ctx* ctx, const double* depth, const void* img_desc_host, int n_img, double pc,
+                               const uint8_t* table_host, const uint8_t* bad_rgba_host, uint8_t* rgba_out, int64_t* n_valid_out,
+                               double* z_out, void* stream);
+psfm_status psfm_ctx_set_depth_display(psfm_ctx* ctx, int timing);
+psfm_status psfm_depth_display_last_ms(psfm_ctx* ctx, double* ms4);
+int psfm_depth_display_chunk(void);
+
 /* Trajectories against ground-truth masks (csrc/psfm_ground_truth.hip; the two per-element rules are csrc/psfm_ground_truth.h).
  * psfm_traj_eval_counts     motion_seg/eval_traj_iou.py:79-115 (per_img_traj_metrics) reduced to what its four metrics are functions
  *                           of: per frame, the counts tp, fp, fn, tn over the labelled points of that frame.  A point (x, y) f64 is

@@ -230,6 +230,11 @@ struct psfm_ctx {
     bool sd_timing = false;              // record events around the fill, the winner pass and the store pass
     hipEvent_t sd_events[4] = {nullptr, nullptr, nullptr, nullptr};
     double sd_ms[3] = {0.0, 0.0, 0.0};
+    // psfm_depth_display (psfm_depth_display.hip): counts | histograms | selection state | descriptors | table; the compacted values
+    PsfmBuf dd_ws, dd_comp;
+    bool dd_timing = false;              // record events around the count, compact, select and colour passes
+    hipEvent_t dd_events[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    double dd_ms[4] = {0.0, 0.0, 0.0, 0.0};
     PsfmBuf gt_flag;                     // psfm_traj_vote_labels (psfm_ground_truth.hip): a present point outside the image
     hipStream_t side_stream = nullptr;   // flow_check of psfm_connect runs here, ahead of the frame loop
     hipStream_t copy_stream = nullptr;   // psfm_load_flo_stack: H2D copies out of the pinned ring

@@ -34,6 +34,7 @@ EXPORTS = [
     "psfm_sparse_depth", "psfm_sparse_depth_sort_ids", "psfm_ctx_set_sparse_depth", "psfm_ctx_get_sparse_depth_budget",
     "psfm_sparse_depth_last_ms", "psfm_colmap_points3d_count", "psfm_colmap_points3d_scan",
     "psfm_ctx_set_motion_boundary", "psfm_motion_boundary", "psfm_kill_map",
+    "psfm_depth_display", "psfm_ctx_set_depth_display", "psfm_depth_display_last_ms", "psfm_depth_display_chunk",
 ]
 
 
@@ -140,6 +141,10 @@ def lib():
     L.psfm_ctx_set_sparse_depth.argtypes = [vp, i64, i32]
     L.psfm_ctx_get_sparse_depth_budget.argtypes = [vp, ctypes.POINTER(i64)]
     L.psfm_sparse_depth_last_ms.argtypes = [vp, ctypes.POINTER(f64)]
+    L.psfm_depth_display.argtypes = [vp, vp, vp, i32, f64, vp, vp, vp, vp, vp, vp]
+    L.psfm_ctx_set_depth_display.argtypes = [vp, i32]
+    L.psfm_depth_display_last_ms.argtypes = [vp, ctypes.POINTER(f64)]
+    L.psfm_depth_display_chunk.argtypes = []
     L.psfm_colmap_points3d_count.argtypes = [vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
     L.psfm_colmap_points3d_scan.argtypes = [vp, ctypes.c_uint64, vp, vp, vp, vp]
     L.psfm_shard_begin.argtypes = [vp, i32, i32, i32, i32, i64, i64, i32, vp, i64, vp]
@@ -248,6 +253,15 @@ class Context:
         ms = (ctypes.c_double * 3)()
         check(lib().psfm_sparse_depth_last_ms(self._h, ms))
         return {"fill_ms": ms[0], "winner_ms": ms[1], "store_ms": ms[2]}
+
+    def set_depth_display(self, timing=False):
+        """psfm_sfm.convert.depth_display_device: events around the count, compact, select and colour passes (depth_display_ms)."""
+        check(lib().psfm_ctx_set_depth_display(self._h, int(bool(timing))))
+
+    def depth_display_ms(self):
+        ms = (ctypes.c_double * 4)()
+        check(lib().psfm_depth_display_last_ms(self._h, ms))
+        return {"count_ms": ms[0], "compact_ms": ms[1], "select_ms": ms[2], "colour_ms": ms[3]}
 
     def set_profiling(self, enable):
         check(lib().psfm_ctx_set_profiling(self._h, int(enable)))   # 0 off, 1 every launch, N>1 every N-th chain_step

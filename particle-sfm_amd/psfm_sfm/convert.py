@@ -9,6 +9,10 @@ sparse_depth_host is the same rules in NumPy, the model the tests compare the de
 pixel = clip(int32(np.round(xy)), 0, size - 1) from the model's xys; depth = ((r20 X + r21 Y) + r22 Z) + t2, each operation rounded
 once; point3D_id -1 is skipped; of several observations of one pixel the last in list order wins; other pixels hold 0.0.
 
+The display PNG (convert.py:26-41, :95) is made either on the host (normalize_depth_for_display, the reference's route) or on the device
+(psfm_depth_display, csrc/psfm_depth_display.hip: the RGBA bytes plt.imsave would write, bit for bit; depth_display_host is the same
+rule in NumPy), or not at all (png=False).
+
 Only .bin models are read: a .txt model raises NotImplementedError (convert it with COLMAP's model_converter).
 """
 import collections
@@ -281,6 +285,13 @@ def sparse_depth_device(model, ctx=None, sort="auto"):
     sort), "device64" (ids below 2^63: its 64-bit record sort), "host" (np.argsort, any id), "auto" (device when every id is below
     2^32, else host).  An observation whose id names no point raises KeyError(the smallest such id of the batch), as the reference's
     dict lookup does; the context stays usable."""
+    for batch in sparse_depth_batches(model, ctx, sort):
+        yield from batch
+
+
+def sparse_depth_batches(model, ctx=None, sort="auto"):
+    """sparse_depth_device one batch at a time: yields [(image name, depth)] whose maps follow each other in one device buffer (what
+    depth_display_device takes)."""
     import ctypes
     import torch
     from point_trajectory import _hip
@@ -322,9 +333,11 @@ def sparse_depth_device(model, ctx=None, sort="auto"):
         if st == _hip.PSFM_ERR_ARG and b"names 3-D point" in L.psfm_last_error():
             raise KeyError(int(missing.value))
         _hip.check(st)
+        batch = []
         for i in range(a, b):
             o, w, h = int(d["out_off"][i - a]), int(d["w"][i - a]), int(d["h"][i - a])
-            yield model.images[i].name, out[o:o + h * w].view(h, w)
+            batch.append((model.images[i].name, out[o:o + h * w].view(h, w)))
+        yield batch
 
 
 # ---- the files ---------------------------------------------------------------------------------------------------------------------------
@@ -343,6 +356,93 @@ def normalize_depth_for_display(depth, pc=98, cmap="binary"):
     return plt.get_cmap(cmap)(inv.astype(np.float32))[:, :, :3]
 
 
+def colour_table(cmap="binary"):
+    """-> (table (256, 4) u8, bad (4,) u8): the bytes plt.imsave writes for colour index 0..255 and for NaN.  The map evaluated by
+    matplotlib, times 255, truncated; alpha 255 (the reference drops alpha, imsave puts 1.0 back).  Data, not a formula: 'binary' is
+    not 255 - i everywhere."""
+    from matplotlib import pyplot as plt
+    cm = plt.get_cmap(cmap)
+    table = (cm(np.arange(256)) * 255).astype(np.uint8)
+    bad = (np.asarray(cm(np.float32(np.nan)), np.float64) * 255).astype(np.uint8)
+    table[:, 3], bad[3] = 255, 255
+    return np.ascontiguousarray(table), np.ascontiguousarray(bad)
+
+
+def percentile_rank(n, q):
+    """np.percentile's 'linear' method on n sorted values -> (j, min(j + 1, n - 1), g): the two order statistics it reads and the
+    weight between them, each operation rounded once as NumPy does."""
+    vi = np.float64(n - 1) * (np.float64(q) / np.float64(100.0))
+    j = int(np.floor(vi))
+    return j, min(j + 1, n - 1), vi - np.float64(j)
+
+
+def percentile_lerp(a, b, g):
+    diff = b - a
+    return b - diff * (np.float64(1.0) - g) if g >= 0.5 else a + diff * g
+
+
+def depth_display_host(depth, pc=98, cmap="binary"):
+    """The display image of one map by the rules of csrc/psfm_depth_display.h in NumPy, element by element what the reference's
+    normalize_depth_for_display followed by plt.imsave's byte conversion gives: -> (rgba (h, w, 4) u8 or None for a map without a
+    positive depth, z1, z2).  The model the tests compare the device with bit for bit."""
+    depth = np.asarray(depth, np.float64)
+    valid = depth > 0
+    n = int(np.count_nonzero(valid))
+    if n == 0:
+        return None, 0.0, 0.0
+    table, bad = colour_table(cmap)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        inv = 1.0 / (depth + 1.0)
+        s = np.sort(inv[valid].view(np.uint64)).view(np.float64)          # (valid inv are >= 0: their bit patterns order like them)
+        z = []
+        for q in (pc, 100 - pc):
+            j, j1, g = percentile_rank(n, q)
+            z.append(percentile_lerp(s[j], s[j1], g))
+        z1, z2 = z
+        v = (inv - z2) / (z1 - z2)
+        v = np.where(v < 0, 0.0, v)                                       # (NaN fails both comparisons and stays)
+        v = np.where(v > 1, 1.0, v)
+        v32 = v.astype(np.float32)
+        xa = v32 * np.float32(256.0)
+        nan = np.isnan(v32)
+        index = np.where(xa == np.float32(256.0), 255, np.where(nan, 0, xa).astype(np.int64))
+    rgba = table[index]
+    rgba[nan] = bad
+    return rgba, float(z1), float(z2)
+
+
+def depth_display_device(maps, pc=98, cmap="binary", ctx=None):
+    """The display images of the device maps of ONE batch of sparse_depth_batches, read where they are: maps = [(h, w) f64 device
+    tensor] that follow each other in one buffer.  -> [(rgba (h, w, 4) u8 device tensor or None, z1, z2)] (psfm_depth_display,
+    csrc/psfm_depth_display.hip); the images are views of one buffer."""
+    import ctypes
+    import torch
+    from point_trajectory import _hip
+    if ctx is None:
+        ctx = _hip.context()
+    maps = list(maps)
+    if not maps:
+        return []
+    d = np.zeros(len(maps), IMAGE_DESC)
+    base, off = maps[0].data_ptr(), 0
+    for i, m in enumerate(maps):
+        if m.dtype != torch.float64 or m.dim() != 2 or not m.is_contiguous() or m.data_ptr() != base + 8 * off:
+            raise ValueError("depth_display_device: map %d is not the next (h, w) f64 map of one batch buffer" % i)
+        d[i]["h"], d[i]["w"], d[i]["out_off"] = m.shape[0], m.shape[1], off
+        off += m.numel()
+    table, bad = colour_table(cmap)
+    out = torch.empty((off, 4), dtype=torch.uint8, device=maps[0].device)
+    n_valid, z = np.zeros(len(maps), np.int64), np.zeros((len(maps), 2), np.float64)
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    _hip.check(_hip.lib().psfm_depth_display(ctx.handle, base, p(d), len(maps), float(pc), p(table), p(bad), _hip.ptr(out), p(n_valid), p(z),
+                                             _hip.current_stream_ptr(ctx.device)))
+    res = []
+    for i, m in enumerate(maps):
+        o = int(d[i]["out_off"])
+        res.append((out[o:o + m.numel()].view(m.shape[0], m.shape[1], 4) if n_valid[i] else None, float(z[i, 0]), float(z[i, 1])))
+    return res
+
+
 def _matplotlib():
     try:
         from matplotlib import pyplot as plt
@@ -352,17 +452,33 @@ def _matplotlib():
         return None
 
 
-def save_model(output_dir, model, device=True, ctx=None):
+DEFAULT_DISPLAY = "device"    # display=None under device=True: 9.5 s against the host route's 16.3 s end to end at 101 x 1080p
+                              # (profiles/EXPERIMENTS.md, section 21)
+
+
+def save_model(output_dir, model, device=True, ctx=None, png=True, display=None, writers=1):
     """Writes depths/NAME.npy (+ .png), poses/NAME.txt, intrinsics/NAME.txt for every image of `model`.  device=True: the maps come
-    from psfm_sparse_depth (a GPU is required); False: from the NumPy model.  The .npy / .png files are written by a writer thread
-    while the device works on the next batch."""
+    from psfm_sparse_depth (a GPU is required); False: from the NumPy model.  png=False: no display PNG is computed or written.
+    display: "host" (normalize_depth_for_display in the writer thread, the reference's route) or "device" (psfm_depth_display on the
+    batch's maps in HBM; device=True only; the writer hands the ready RGBA bytes to the same plt.imsave); None: "host" without a
+    device, DEFAULT_DISPLAY with one.  The .npy / .png files are written by `writers` threads (zlib releases the GIL; the files do not
+    depend on their number) while the device works on the next batch."""
+    if display is None:
+        display = DEFAULT_DISPLAY if device else "host"
+    if display not in ("host", "device"):
+        raise ValueError("display must be 'host' or 'device'")
+    if display == "device" and not device:
+        raise ValueError("display='device' needs device=True: the maps of the NumPy model are not in device memory")
+    writers = int(writers)
+    if writers < 1:
+        raise ValueError("writers must be >= 1")
     depth_dir, pose_dir, intr_dir = (os.path.join(output_dir, n) for n in ("depths", "poses", "intrinsics"))
     for p in (depth_dir, pose_dir, intr_dir):
         os.makedirs(p, exist_ok=True)
     stem = lambda name: os.path.splitext(name)[0]
     for im in model.images:
         np.savetxt(os.path.join(intr_dir, stem(im.name) + ".txt"), intrinsics(model.cameras[im.camera_id]))
-    plt = _matplotlib()
+    plt = _matplotlib() if png else None
     q, failed = queue.Queue(maxsize=8), []
 
     def writer():
@@ -373,23 +489,34 @@ def save_model(output_dir, model, device=True, ctx=None):
             if failed:
                 continue                                                  # (keep draining: the producer must not block)
             try:
-                name, depth = item
+                name, depth, img = item
                 np.save(os.path.join(depth_dir, stem(name) + ".npy"), depth)
-                img = normalize_depth_for_display(depth) if plt is not None else None
+                if img is None and plt is not None and display == "host":
+                    img = normalize_depth_for_display(depth)
                 if img is not None:
                     plt.imsave(os.path.join(depth_dir, stem(name) + ".png"), img)
             except BaseException as e:                                    # noqa: B902 -- handed to the caller below
                 failed.append(e)
 
-    th = threading.Thread(target=writer, name="psfm-depth-writer")
-    th.start()
+    threads = [threading.Thread(target=writer, name="psfm-depth-writer-%d" % k) for k in range(writers)]
+    for th in threads:
+        th.start()
     try:
-        maps = sparse_depth_device(model, ctx) if device else sparse_depth_host(model)
-        for name, depth in maps:
-            q.put((name, depth.cpu().numpy() if device else depth))
+        if device:
+            for batch in sparse_depth_batches(model, ctx):
+                imgs = [None] * len(batch)
+                if display == "device" and plt is not None:
+                    imgs = [r[0] for r in depth_display_device([d for _, d in batch], ctx=ctx)]
+                for (name, depth), img in zip(batch, imgs):
+                    q.put((name, depth.cpu().numpy(), None if img is None else img.cpu().numpy()))
+        else:
+            for name, depth in sparse_depth_host(model):
+                q.put((name, depth, None))
     finally:
-        q.put(None)
-        th.join()
+        for _ in threads:
+            q.put(None)
+        for th in threads:
+            th.join()
     if failed:
         raise failed[0]
     for im in model.images:
@@ -397,10 +524,10 @@ def save_model(output_dir, model, device=True, ctx=None):
         np.savetxt(os.path.join(pose_dir, stem(im.name) + ".txt"), Rt)
 
 
-def save_depth_pose(output_dir, cameras, images, points3D, device=True):
+def save_depth_pose(output_dir, cameras, images, points3D, device=True, png=True, display=None, writers=1):
     """The reference's signature: its three dicts (any mappings of objects with the same attributes)."""
-    save_model(output_dir, model_from_dicts(cameras, images, points3D), device=device)
+    save_model(output_dir, model_from_dicts(cameras, images, points3D), device=device, png=png, display=display, writers=writers)
 
 
-def write_depth_pose_from_colmap_format(input_dir, output_dir, device=True):
-    save_model(output_dir, read_model_arrays(input_dir), device=device)
+def write_depth_pose_from_colmap_format(input_dir, output_dir, device=True, png=True, display=None, writers=1):
+    save_model(output_dir, read_model_arrays(input_dir), device=device, png=png, display=display, writers=writers)
