@@ -91,7 +91,8 @@ typedef struct psfm_track_info {
     int64_t solver_iterations; /* total trust-region iterations over all frames (track_optimize) */
     int32_t n_solves;
     int32_t chain_mode;        /* how the frame recurrence ran: 1 one launch per frame, 2 one persistent launch, 3 one launch per
-                                  frame for a whole batch of sequences (psfm_connect_batch) */
+                                  frame for a whole batch of sequences (psfm_connect_batch), 4 one launch per direction over
+                                  caller-given query points (psfm_track_queries) */
 } psfm_track_info;
 
 const char* psfm_last_error(void);
@@ -252,6 +253,31 @@ psfm_status psfm_track(psfm_ctx* ctx, const float* flows, const uint8_t* occ, co
 psfm_status psfm_connect(psfm_ctx* ctx, const float* flows_f, const float* flows_b, const float* flows_f2,
                          const float* flows_b2, int n_flows, int h, int w, float thres, int sample_ratio,
                          uint8_t* occ, uint8_t* occ_s2, psfm_track_info* info_host, void* stream);
+
+/* Caller-given QUERY POINTS tracked through a flow stack: for every query q -- a position q_xy[q] at frame q_t[q],
+ * 0 <= q_t[q] <= n_flows -- the body of track.py:37-47 for that one position: flow_sample = grid_sample(flows[f], p)
+ * (trajectory.py:25-37), next, alive = step_forward(p, flow_sample, occ[f], mb) (trajectory.py:45-62), at f = t, t+1, ...; the track
+ * ends at the first step that is not alive, or at frame n_flows.  No grid, no respawn, no id assignment: a query interacts with no
+ * other track.  The kill rule is the shipped one (trajectory.py:61), or the motion-boundary form (:60) when the context has
+ * psfm_ctx_set_motion_boundary on; the kill maps are then built from the stack being sampled.
+ *   flows_f (n_flows,H,W,2) f32, occ_f (n_flows,H,W) u8   the forward stack and its occlusion maps, or both NULL
+ *   flows_b, occ_b   the BACKWARD stack -- flows_b[f] is the flow from frame f+1 to frame f -- and ITS occlusion maps, that is
+ *                    flow_check(flows_b, flows_f), or both NULL.  A query at frame t samples map t-1 and moves to frame t-1, down to 0
+ *   q_xy (n_q,2) f64, q_t (n_q) i32   on the DEVICE
+ * At least one stack must be given; maps are densely packed.  With both stacks a query is tracked both ways and the two halves are one
+ * trajectory: points in ascending time, the query point once, birth = t - (len_b - 1), len = len_b + len_f - 1.
+ * Queries outside the image are legal (all taps out of bounds, flow 0, next position invalid: length 1).  Refused with PSFM_ERR_ARG,
+ * BEFORE anything is tracked and with the previous result intact: a query with a non-finite coordinate or a frame outside
+ * [0, n_flows] -- psfm_last_error() names the first such index -- no stack or a stack without its maps, n_q outside [0, 2^28)
+ * (a frame row of the position slab, 16 bytes per query, stays below 4 GB; checked before any allocation).
+ * The result REPLACES the context's result set as psfm_track does -- trajectory i is query i, len >= 1; info->n_traj = n_q,
+ * info->chain_mode = 4 -- and every consumer of a result works on it unchanged (psfm_result_device / _copy, psfm_result_filter /
+ * _filtered_copy, psfm_window_sample, psfm_traj_to_matches, the label merge), except psfm_result_keys, whose key needs a birth grid
+ * index: it refuses a query result (PSFM_ERR_ARG).  Identical calls give identical bytes.  Synchronises `stream`.
+ * Out of scope: path consistency for query tracks, tracking through occlusion, several sequences per call. */
+psfm_status psfm_track_queries(psfm_ctx* ctx, const float* flows_f, const uint8_t* occ_f, const float* flows_b, const uint8_t* occ_b,
+                               int n_flows, int h, int w, const double* q_xy, const int32_t* q_t, int64_t n_q,
+                               psfm_track_info* info_host, void* stream);
 
 /* The loop of the reference's driver over a directory of sequences (run_particlesfm.py:168-176 -> connect_point_trajectory ->
  * main_connect_point_trajectories.py:36-53 per sequence) for n_seq sequences of the SAME frame size and sample ratio (any

@@ -180,7 +180,7 @@ extern "C" psfm_status psfm_ctx_destroy(psfm_ctx* c)
                        &c->handoff, &c->seg_info, &c->seg_table, &c->persist_bar, &c->batch_tab, &c->batch_ws, &c->batch_fc, &c->win_ws, &c->flt_ids, &c->flt_birth, &c->flt_len, &c->flt_off, &c->flt_xy,
                        &c->mt_kp_off, &c->mt_q, &c->mt_pts, &c->mt_kp_ind, &c->mt_kp_xy, &c->mt_moff, &c->mt_keys, &c->mt_rows, &c->mt_gid, &c->mt_pairs,
                        &c->lb_state, &c->lb_first, &c->lb_flag, &c->lb_ws, &c->lb_ids, &c->lb_off, &c->lb_frames, &c->lb_xy, &c->lb_labels, &c->gt_flag, &c->kill,
-                       &c->db_kp, &c->db_pairs, &c->db_rows, &c->db_ws, &c->sd_ws, &c->dd_ws, &c->dd_comp};
+                       &c->db_kp, &c->db_pairs, &c->db_rows, &c->db_ws, &c->sd_ws, &c->dd_ws, &c->dd_comp, &c->qr_ws};
     for (auto b : bufs) b->release();
     for (hipEvent_t e : c->sd_events) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->dd_events) if (e) (void)hipEventDestroy(e);
@@ -503,6 +503,7 @@ static psfm_status psfm_track_impl(psfm_ctx* c, const float* flows, const uint8_
     c->solve_stats.clear();
     c->res_n_traj = c->res_n_points = 0;
     c->res_n_flows = n_flows;
+    c->res_is_query = false;
     c->pc_persist_ok = device_is_ours || c->resident_budget > 0;
     c->pc_giveups = 0;
 

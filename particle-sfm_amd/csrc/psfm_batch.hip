@@ -169,6 +169,7 @@ static psfm_status batch_run(psfm_ctx* const* ctxs, int n_seq, const float* cons
             c->solve_stats.clear();
             c->res_n_traj = c->res_n_points = 0;
             c->res_n_flows = n_flows[i];
+            c->res_is_query = false;
             c->pc_persist_ok = false;
             c->pc_giveups = 0;
             c->n_fused_ok = c->n_fused_redone = c->n_chain = 0;

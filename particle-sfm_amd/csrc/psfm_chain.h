@@ -98,10 +98,12 @@ __device__ __forceinline__ void psfm_step_pin(PsfmStepLoads& L)
     if (MASKS) asm volatile("" : "+v"(L.onw), "+v"(L.one), "+v"(L.osw), "+v"(L.ose));
 }
 
-template <class A>
+// FAST = false: the tap geometry with the TRUE division (psfm_taps), for a position outside the proven domain of psfm_div_r -- a
+// caller-given one (psfm_query.h); issue and finish of one step take the same form.
+template <bool FAST = true, class A>
 __device__ __forceinline__ PsfmStepLoads psfm_step_issue(const A& a, double2 p)
 {
-    const PsfmTaps t = psfm_taps_fast((float)p.x, (float)p.y, a.cw, a.ch, a.rcw, a.rch, a.H, a.W);
+    const PsfmTaps t = psfm_taps_t<FAST>((float)p.x, (float)p.y, a.cw, a.ch, a.rcw, a.rch, a.H, a.W);
     const PsfmTapIdx k = psfm_tap_idx(a.H, a.W, t);   // flow and occlusion map share the tap geometry
     PsfmStepLoads L;
     const unsigned onw = (unsigned)k.nw, one = (unsigned)k.ne, osw = (unsigned)k.sw, ose = (unsigned)k.se;
@@ -114,10 +116,10 @@ __device__ __forceinline__ PsfmStepLoads psfm_step_issue(const A& a, double2 p)
 // MB (the motion-boundary option, trajectory.py:51-53,60): the mask bytes are KILL-MAP bytes -- bit 0 occlusion, bit 1 motion boundary
 // (psfm_motion_boundary.h) -- and give two verdicts through the same taps, each compared on its own: alive = valid & !occ & !mb.
 // (One verdict over occ | mb is another rule: two taps of weight 0.06, one occluded, one on a boundary, would kill.)
-template <bool MB = false, class A>
+template <bool MB = false, bool FAST = true, class A>
 __device__ __forceinline__ PsfmStep psfm_step_finish(const A& a, double2 p, const PsfmStepLoads& L)
 {
-    const PsfmTaps t = psfm_taps_fast((float)p.x, (float)p.y, a.cw, a.ch, a.rcw, a.rch, a.H, a.W);
+    const PsfmTaps t = psfm_taps_t<FAST>((float)p.x, (float)p.y, a.cw, a.ch, a.rcw, a.rch, a.H, a.W);
     const int x0 = t.x0, y0 = t.y0, x1 = t.x0 + 1, y1 = t.y0 + 1;
     const bool xw = (x0 >= 0) & (x0 < a.W), xe = (x1 >= 0) & (x1 < a.W);
     const bool yn = (y0 >= 0) & (y0 < a.H), ys = (y1 >= 0) & (y1 < a.H);

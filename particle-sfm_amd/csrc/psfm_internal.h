@@ -168,6 +168,9 @@ struct psfm_ctx {
     PsfmBuf res_birth, res_len, res_off, res_xy;
     int64_t res_n_traj = 0, res_n_points = 0;
     int res_n_flows = 0;           // flows of the sequence the result came from (psfm_result_keys checks its packed key)
+    bool res_is_query = false;     // the result is psfm_track_queries': trajectory i is query i, no birth grid index (psfm_result_keys
+                                   // refuses it); cleared by every other entry point that replaces the result
+    PsfmBuf qr_ws;                 // psfm_track_queries (psfm_query.hip): first refused query | lengths per direction | scan storage
     // solver workspace
     PsfmBuf sol_x, sol_state, sol_partials, sol_ctrl, sol_misc, sol_stats, sol_fused, sol_bar;
     PsfmBuf sol_list;              // launch chain / resident solve: per block, the lanes that take part in the solve (pc_build_list)

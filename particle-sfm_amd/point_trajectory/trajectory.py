@@ -425,3 +425,70 @@ def run_track(flows, occ_maps, flows_f2, occ_maps_s2, sample_ratio, return_devic
     if return_device:
         return info
     return _result_to_host(ctx, info)
+
+
+def run_track_queries(xy, t, flows=None, occ=None, flows_b=None, occ_b=None, motion_boundary=False, mb_thres=0.02, return_device=False):
+    """Caller-given query points tracked through a flow stack in ONE psfm_track_queries call: query i is the position xy[i] ((Q,2)
+    float64) at frame t[i] ((Q,) int, 0 <= t <= n_flows); per query the body of track.py:37-47 (grid_sample + step_forward) until the
+    first step that is not alive or the end of the stack.
+    flows / occ: the forward stack (n,H,W,2) and its occlusion maps (n,H,W); flows_b / occ_b: the BACKWARD stack (flows_b[f]: frame
+    f+1 -> f) and ITS occlusion maps, flow_check(flows_b, flows).  One stack: tracked that way; both: both ways, one trajectory.
+    Returns a TrajectoryList whose trajectory i is query i (length >= 1); the result also replaces the context's result set, so the
+    consumers of a tracking result (result_to_trajectory_set, sample_window_device, match_tables_device ...) work on it.
+    A non-finite coordinate or a frame outside [0, n_flows] raises PsfmError (status PSFM_ERR_ARG) naming the first such query."""
+    import torch
+    ctx = _hip.context()
+    dev = torch.device("cuda", ctx.device)
+    fl = oc = fb = ob = None
+    if flows is not None:
+        fl = _as_device_stack(flows, torch.float32, (1, 1, 2))
+    if occ is not None:
+        oc = _as_device_stack(occ, torch.uint8, (1, 1))
+    if flows_b is not None:
+        fb = _as_device_stack(flows_b, torch.float32, (1, 1, 2))
+    if occ_b is not None:
+        ob = _as_device_stack(occ_b, torch.uint8, (1, 1))
+    ref = fl if fl is not None else fb
+    if ref is None:
+        n, H, W = 0, 0, 0                 # (refused by the library: no stack given)
+    else:
+        n, H, W = int(ref.shape[0]), int(ref.shape[1]), int(ref.shape[2])
+        for name, m, tail in (("flows", fl, (H, W, 2)), ("occ", oc, (H, W)), ("flows_b", fb, (H, W, 2)), ("occ_b", ob, (H, W))):
+            if m is not None and (int(m.shape[0]) != n or tuple(m.shape[1:]) != tail):
+                raise ValueError("track_queries: %s has shape %s, expected %s" % (name, tuple(m.shape), (n,) + tail))
+
+    def as_t(a, dt):
+        a = a.detach() if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
+        return a.to(device=dev, dtype=dt)
+    q_xy = as_t(xy, torch.float64).reshape(-1, 2).contiguous()
+    q_t = as_t(t, torch.int32).reshape(-1).contiguous()
+    if q_t.shape[0] != q_xy.shape[0]:
+        raise ValueError("track_queries: %d positions for %d frames" % (q_xy.shape[0], q_t.shape[0]))
+    info = _hip.TrackInfo()
+    with _MotionBoundary(ctx, motion_boundary, mb_thres):
+        st = _hip.lib().psfm_track_queries(ctx.handle, _hip.ptr(fl), _hip.ptr(oc), _hip.ptr(fb), _hip.ptr(ob), n, H, W, _hip.ptr(q_xy),
+                                           _hip.ptr(q_t), int(q_xy.shape[0]), ctypes.byref(info), _hip.current_stream_ptr(ctx.device))
+    _hip.check(st)
+    if return_device:
+        return info
+    return _result_to_host(ctx, info)
+
+
+def run_connect_queries(xy, t, flows_f, flows_b, thres=1.0, direction="forward", motion_boundary=False, mb_thres=0.02, return_device=False):
+    """flow_check + run_track_queries: the occlusion maps each direction needs come from flow_check_device in that direction's own
+    orientation -- forward: flow_check(flows_f, flows_b); backward: flow_check(flows_b, flows_f).  direction: "forward", "backward"
+    or "both".  flows_f, flows_b: (n,H,W,2) stacks, flows_b[f] being the flow from frame f+1 to frame f."""
+    import torch
+    from .utils import flow_check_device
+    if direction not in ("forward", "backward", "both"):
+        raise ValueError("connect_queries: direction must be 'forward', 'backward' or 'both'")
+    ff = _as_device_stack(flows_f, torch.float32, (1, 1, 2))
+    fb = _as_device_stack(flows_b, torch.float32, (1, 1, 2))
+    n = min(int(ff.shape[0]), int(fb.shape[0]))
+    ff, fb = ff[:n], fb[:n]
+    kw = {}
+    if direction in ("forward", "both"):
+        kw.update(flows=ff, occ=flow_check_device(ff, fb, thres)[1])
+    if direction in ("backward", "both"):
+        kw.update(flows_b=fb, occ_b=flow_check_device(fb, ff, thres)[1])
+    return run_track_queries(xy, t, motion_boundary=motion_boundary, mb_thres=mb_thres, return_device=return_device, **kw)
