@@ -10,12 +10,16 @@
 // more than PSFM_SORT64_MAX_N records and behind PSFM_FIN_SORT=0), lengths are scanned into offsets, and the
 // frame-major log is transposed into a track-major (n_points,2) f64 array through LDS tiles so that
 // both the slab reads (consecutive lanes) and the result writes (consecutive times) are coalesced.
+//
+// What a call DECIDES (key width, sort bits, which sort, which half of sort_keys the compaction fills, group plan or decode + scan) is
+// psfm_fin_form() of psfm_finalize_plan.h, computed once by each entry point; that header also holds the only code that takes a key apart.
 #include <cstring>
 #include <stdio.h>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
 #include "psfm_device.h"
+#include "psfm_finalize_plan.h"
 #include "psfm_internal.h"
 
 #define PSFM_BLOCK 256
@@ -71,26 +75,7 @@ __global__ __launch_bounds__(PSFM_BLOCK) void psfm_collect_alive_kernel(
     psfm_collect_alive_body(birth_frame, birth_idx, ctr, shards, fin_keys, fin_lanes, cap, shard_cap, last_time, shift_b, shift_d);
 }
 
-// The sort key (last << shift_d | birth << shift_b | idx) has birth <= last: the pair (last, birth) is re-coded as the
-// triangular index last*(last+1)/2 + birth, which orders like the pair and needs ~1 bit less.  When that makes the key
-// fit 32 bits (100 frames at 1080p/r=2: 13 + 19) the radix sort runs on 4-byte keys in 4 passes instead of 8-byte
-// keys in 5.
-struct PsfmKeyFmt { int shift_b, shift_d; int use32; };
-__device__ __forceinline__ unsigned psfm_key32(unsigned long long k, const PsfmKeyFmt& f)
-{
-    const unsigned last = (unsigned)(k >> f.shift_d);
-    const unsigned birth = (unsigned)((k >> f.shift_b) & ((1ull << (f.shift_d - f.shift_b)) - 1ull));
-    const unsigned idx = (unsigned)(k & ((1ull << f.shift_b) - 1ull));
-    return ((last * (last + 1u) / 2u + birth) << f.shift_b) | idx;
-}
-__device__ __forceinline__ void psfm_put_key(unsigned long long* keys, int64_t pos, unsigned long long k, const PsfmKeyFmt& f)
-{
-    if (f.use32) ((unsigned*)keys)[pos] = psfm_key32(k, f);
-    else keys[pos] = k;
-}
-
 // gather the per-shard record slices into one contiguous (key, lane) array for the sort
-struct PsfmShardOffsets { int count[PSFM_NSHARD]; int64_t start[PSFM_NSHARD]; };
 __global__ __launch_bounds__(PSFM_BLOCK) void psfm_compact_shards_kernel(
     const unsigned long long* __restrict__ fin_keys, const int* __restrict__ fin_lanes, int shard_cap,
     PsfmShardOffsets so, unsigned long long* __restrict__ keys, int* __restrict__ lanes, PsfmKeyFmt fmt)
@@ -104,37 +89,17 @@ __global__ __launch_bounds__(PSFM_BLOCK) void psfm_compact_shards_kernel(
 }
 
 // sorted record i (== trajectory id) -> birth, length (i32) and length as i64 for the offset scan
-__global__ __launch_bounds__(PSFM_BLOCK) void psfm_decode_kernel(const unsigned long long* __restrict__ keys, int64_t n,
-                                                                 int shift_b, int shift_d, int* __restrict__ birth,
-                                                                 int* __restrict__ len, int64_t* __restrict__ len64)
+__global__ __launch_bounds__(PSFM_BLOCK) void psfm_decode_kernel(const void* __restrict__ keys, int64_t n, PsfmKeyFmt fmt,
+                                                                 int* __restrict__ birth, int* __restrict__ len, int64_t* __restrict__ len64)
 {
     const int64_t i = (int64_t)blockIdx.x * PSFM_BLOCK + threadIdx.x;
     if (i > n) return;
     if (i == n) { len64[i] = 0; return; }
-    const unsigned long long k = keys[i];
-    const int last = (int)(k >> shift_d);
-    const int b = (int)((k >> shift_b) & ((1ull << (shift_d - shift_b)) - 1ull));
+    int last, b, idx;
+    psfm_key_fields(keys, i, fmt.use32, fmt.shift_b, fmt.shift_d, &last, &b, &idx);
     birth[i] = b;
     len[i] = last - b + 1;
     len64[i] = (int64_t)(last - b + 1);
-}
-
-__global__ __launch_bounds__(PSFM_BLOCK) void psfm_decode32_kernel(const unsigned* __restrict__ keys, int64_t n, int shift_b,
-                                                                   int* __restrict__ birth, int* __restrict__ len,
-                                                                   int64_t* __restrict__ len64)
-{
-    const int64_t i = (int64_t)blockIdx.x * PSFM_BLOCK + threadIdx.x;
-    if (i > n) return;
-    if (i == n) { len64[i] = 0; return; }
-    const unsigned tri = keys[i] >> shift_b;
-    // last = the largest l with l*(l+1)/2 <= tri
-    int l = (int)((sqrtf(8.0f * (float)tri + 1.0f) - 1.0f) * 0.5f);
-    while (l > 0 && (unsigned)l * (unsigned)(l + 1) / 2u > tri) --l;
-    while ((unsigned)(l + 1) * (unsigned)(l + 2) / 2u <= tri) ++l;
-    const int b = (int)(tri - (unsigned)l * (unsigned)(l + 1) / 2u);
-    birth[i] = b;
-    len[i] = l - b + 1;
-    len64[i] = (int64_t)(l - b + 1);
 }
 
 // ---- offsets without a scan over the trajectories ----
@@ -147,43 +112,12 @@ __global__ __launch_bounds__(PSFM_BLOCK) void psfm_decode32_kernel(const unsigne
 // plan swept over chunks of 16 384 groups by one block, counts back to front and offsets front to back with the carries across the
 // chunk edges -- 81 k groups at 1080p x 401 frames cost 55 us more than decode + scan over 6.9 M trajectories, 502 k groups at
 // 480 x 640 x 1000 frames 720 us more than over 10.7 M: profiles/EXPERIMENTS.md 20.)
-#define PSFM_PLAN_MAX_GROUPS 16384
 #define PSFM_PLAN_BLOCK 1024
 struct PsfmPlan {
     const int* gstart; const int64_t* goff;      // gstart == nullptr: birth / len / off are read from the arrays below instead
     const void* keys; int use32, shift_b, shift_d;
     int* birth_w; int* len_w; int64_t* off_w;    // where the gather stores what it computed (the result arrays)
 };
-__device__ __forceinline__ void psfm_tri_invert(unsigned tri, int* last, int* birth)
-{
-    // last = the largest l with l*(l+1)/2 <= tri
-    int l = (int)((sqrtf(8.0f * (float)tri + 1.0f) - 1.0f) * 0.5f);
-    while (l > 0 && (unsigned)l * (unsigned)(l + 1) / 2u > tri) --l;
-    while ((unsigned)(l + 1) * (unsigned)(l + 2) / 2u <= tri) ++l;
-    *last = l;
-    *birth = (int)(tri - (unsigned)l * (unsigned)(l + 1) / 2u);
-}
-__device__ __forceinline__ void psfm_key_fields(const void* keys, int64_t id, int use32, int shift_b, int shift_d, int* last, int* birth, int* idx)
-{
-    if (use32) {
-        const unsigned k = ((const unsigned*)keys)[id];
-        psfm_tri_invert(k >> shift_b, last, birth);
-        *idx = (int)(k & ((1u << shift_b) - 1u));
-    } else {
-        const unsigned long long k = ((const unsigned long long*)keys)[id];
-        *last = (int)(k >> shift_d);
-        *birth = (int)((k >> shift_b) & ((1ull << (shift_d - shift_b)) - 1ull));
-        *idx = (int)(k & ((1ull << shift_b) - 1ull));
-    }
-}
-__device__ __forceinline__ int psfm_key_group(const void* keys, int64_t id, int use32, int shift_b, int shift_d)
-{
-    if (use32) return (int)(((const unsigned*)keys)[id] >> shift_b);      // the 32-bit key carries the group number itself
-    const unsigned long long k = ((const unsigned long long*)keys)[id];
-    const unsigned last = (unsigned)(k >> shift_d);
-    const unsigned birth = (unsigned)((k >> shift_b) & ((1ull << (shift_d - shift_b)) - 1ull));
-    return (int)(last * (last + 1u) / 2u + birth);
-}
 
 // marks[g] = the first sorted record of group g (the array arrives filled with -1: groups nobody marks are empty)
 __global__ __launch_bounds__(PSFM_BLOCK) void psfm_group_bounds_kernel(const void* __restrict__ keys, int64_t n, int use32, int shift_b,
@@ -411,10 +345,7 @@ __global__ __launch_bounds__(PSFM_BLOCK) void psfm_gather_delta_kernel(const flo
         s_len[tid] = l;
         if (ok) {
             atomicMax(&s_maxlen, l);
-            if (idx < 0) {
-                const unsigned long long mask = (1ull << shift_b) - 1ull;
-                idx = (int)((use32 ? (unsigned long long)((const unsigned*)keys)[id] : ((const unsigned long long*)keys)[id]) & mask);
-            }
+            if (idx < 0) idx = psfm_key_idx(psfm_key_at(keys, id, use32), shift_b);
             const int gy = idx / GW, gx = idx - gy * GW;
             s_pos[tid] = make_double2((double)(gx * ratio), (double)(gy * ratio));   // trajectory.py:110-115
         }
@@ -473,90 +404,87 @@ __global__ __launch_bounds__(PSFM_BLOCK) void psfm_gather_delta_kernel(const flo
     }
 }
 
-// key format of a sequence: 32-bit triangular keys when they fit
-static PsfmKeyFmt psfm_key_fmt(const PsfmTrackDims& d, unsigned* end_bit)
+// ---- host side: the plan of a call, where its compaction writes, its sort ----
+// n_seq > 0: a batch of that many sequences (d: common shifts, the longest sequence's time range)
+static PsfmFinForm psfm_form_of(const PsfmTrackDims& d, int64_t n, int n_seq = 0)
 {
-    PsfmKeyFmt f;
-    f.shift_b = d.shift_b; f.shift_d = d.shift_d;
-    const long long lmax = (long long)d.n_flows + 1;            // last valid time <= n_flows
-    const long long tri_max = lmax * (lmax + 1) / 2 + lmax;
-    int tri_bits = 1;
-    while ((1ll << tri_bits) <= tri_max) ++tri_bits;
-    f.use32 = (tri_bits + d.shift_b <= 32) ? 1 : 0;
-    int tbits = 1;
-    while ((1ll << tbits) < (long long)d.n_flows + 2) ++tbits;
-    *end_bit = f.use32 ? (unsigned)(tri_bits + d.shift_b) : (unsigned)(d.shift_d + tbits);
-    return f;
+    static const int sort_on = getenv("PSFM_FIN_SORT") ? atoi(getenv("PSFM_FIN_SORT")) : 1;      // 0: rocPRIM's device sort; 2: the own sort at any size (A/B, tests)
+    static const int plan_on = getenv("PSFM_FIN_PLAN") ? atoi(getenv("PSFM_FIN_PLAN")) : 1;      // 0: decode + scan always (A/B, tests)
+    return psfm_fin_form(d.shift_b, d.shift_d, d.n_flows, n_seq > 0 ? n_seq : 1, n, sort_on, plan_on, n_seq > 0 ? 0 : 1);
 }
 
-// Which half of sort_keys / sort_lanes the compaction fills: the second (rocPRIM sorts second half -> first half), unless this
-// library's own sort (psfm_sort.hip, 32- or 64-bit keys) runs an even number of passes -- it ping-pongs between the halves and has to
-// END in the first.
-// 64-bit keys: the own sort up to PSFM_SORT64_MAX_N records, rocPRIM's above -- inside the finalize the own sort wins where the sort is
-// bound by its launches and loses where it is bound by bandwidth (its scatter kernel holds two blocks per CU: 53 KB of LDS each);
-// figures by record count in profiles/EXPERIMENTS.md 20.
-#define PSFM_SORT64_MAX_N 5000000ll
-static bool psfm_own_sort(const PsfmKeyFmt& fmt, int64_t n)
+// where the compaction writes n records: the halves of sort_keys / sort_lanes the sort reads first (a half = n entries of the key
+// format's width: 4 or 8 bytes)
+struct PsfmFinDst { unsigned long long* keys; int* lanes; };
+static PsfmFinDst psfm_compact_dst(psfm_ctx* c, const PsfmFinForm& f, int64_t n)
 {
-    static const int on = getenv("PSFM_FIN_SORT") ? atoi(getenv("PSFM_FIN_SORT")) : 1;      // 0: rocPRIM's device sort; 2: the own sort at any size (A/B, tests)
-    return on && n < (1ll << 31) && (fmt.use32 || on == 2 || n <= PSFM_SORT64_MAX_N);
-}
-static int psfm_own_sort_passes(const PsfmKeyFmt& fmt, unsigned end_bit)
-{
-    return fmt.use32 ? psfm_sort_pairs32_passes(end_bit) : psfm_sort_pairs64_passes(end_bit);
-}
-static bool psfm_records_in_first_half(const PsfmTrackDims& d, int64_t n)
-{
-    unsigned end_bit = 0;
-    const PsfmKeyFmt fmt = psfm_key_fmt(d, &end_bit);
-    return psfm_own_sort(fmt, n) && (psfm_own_sort_passes(fmt, end_bit) % 2 == 0);
+    const int64_t half = f.first_half ? 0 : n;
+    return {f.fmt.use32 ? (unsigned long long*)(c->sort_keys.as<unsigned>() + half) : c->sort_keys.as<unsigned long long>() + half,
+            c->sort_lanes.as<int>() + half};
 }
 
-// common tail: (key, lane) records already compacted into the halves of sort_keys / sort_lanes psfm_records_in_first_half() names
-// (keys in the format psfm_key_fmt() chose: 8-byte or 4-byte entries, a half = n entries of that width)
-static psfm_status psfm_finalize_sorted(psfm_ctx* c, const PsfmTrackDims& d, int64_t n, int64_t npts, bool delta_log, hipStream_t s)
+template <class K>
+static psfm_status psfm_rocprim_sort(psfm_ctx* c, int64_t n, unsigned end_bit, size_t scan_bytes, hipStream_t s)
+{
+    K* k_out = c->sort_keys.as<K>(), *k_in = k_out + n;
+    int* l_out = c->sort_lanes.as<int>(), *l_in = l_out + n;
+    size_t tmp_bytes = 0;
+    psfm_status st;
+    PSFM_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, k_in, k_out, l_in, l_out, (size_t)n, 0u, end_bit, s));
+    if ((st = c->sort_tmp.ensure(tmp_bytes > scan_bytes ? tmp_bytes : scan_bytes)) != PSFM_OK) return st;
+    PSFM_HIP(rocprim::radix_sort_pairs(c->sort_tmp.p, tmp_bytes, k_in, k_out, l_in, l_out, (size_t)n, 0u, end_bit, s));
+    return PSFM_OK;
+}
+
+// Sorts the n compacted records (psfm_compact_dst) by the plan's key bits into the first halves of sort_keys / sort_lanes.  sort_tmp is
+// sized for the offset scan over n + 1 entries as well (*scan_bytes), BEFORE the sort's launches: growing the buffer frees it.
+static psfm_status psfm_sort_records(psfm_ctx* c, const PsfmFinForm& f, int64_t n, size_t* scan_bytes, hipStream_t s)
 {
     psfm_status st;
-    unsigned end_bit = 0;
-    const PsfmKeyFmt fmt = psfm_key_fmt(d, &end_bit);
-    int* l_in = c->sort_lanes.as<int>() + n;
-    int* l_out = c->sort_lanes.as<int>();
-    size_t tmp_bytes = 0, scan_bytes = 0;
-    PSFM_HIP(rocprim::exclusive_scan(nullptr, scan_bytes, (int64_t*)nullptr, (int64_t*)nullptr, (int64_t)0,
+    PSFM_HIP(rocprim::exclusive_scan(nullptr, *scan_bytes, (int64_t*)nullptr, (int64_t*)nullptr, (int64_t)0,
                                      (size_t)(n + 1), rocprim::plus<int64_t>(), s));
     c->fin_sort_form = 0; c->fin_offsets_form = 0;
-    if (psfm_own_sort(fmt, n)) {
-        if ((st = c->sort_tmp.ensure(scan_bytes)) != PSFM_OK) return st;      // (before the sort's launches: growing the buffer frees it)
-        if (fmt.use32) st = psfm_sort_pairs32(c, c->sort_keys.as<unsigned>(), l_out, c->sort_keys.as<unsigned>() + n, l_in, n, end_bit, s);
-        else st = psfm_sort_pairs64(c, c->sort_keys.as<unsigned long long>(), l_out, c->sort_keys.as<unsigned long long>() + n, l_in, n, end_bit, s);
-        if (st != PSFM_OK) return st;
-        c->fin_sort_form = fmt.use32 ? 1 : 2;
-    } else if (fmt.use32) {
-        unsigned* k_in = c->sort_keys.as<unsigned>() + n;
-        unsigned* k_out = c->sort_keys.as<unsigned>();
-        PSFM_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, k_in, k_out, l_in, l_out, (size_t)n, 0u, end_bit, s));
-        if ((st = c->sort_tmp.ensure(tmp_bytes > scan_bytes ? tmp_bytes : scan_bytes)) != PSFM_OK) return st;
-        PSFM_HIP(rocprim::radix_sort_pairs(c->sort_tmp.p, tmp_bytes, k_in, k_out, l_in, l_out, (size_t)n, 0u, end_bit, s));
-        c->fin_sort_form = 3;
+    if (f.sort_form == 3) {
+        st = f.fmt.use32 ? psfm_rocprim_sort<unsigned>(c, n, f.end_bit, *scan_bytes, s) : psfm_rocprim_sort<unsigned long long>(c, n, f.end_bit, *scan_bytes, s);
     } else {
-        unsigned long long* k_in = c->sort_keys.as<unsigned long long>() + n;
-        unsigned long long* k_out = c->sort_keys.as<unsigned long long>();
-        PSFM_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, k_in, k_out, l_in, l_out, (size_t)n, 0u, end_bit, s));
-        if ((st = c->sort_tmp.ensure(tmp_bytes > scan_bytes ? tmp_bytes : scan_bytes)) != PSFM_OK) return st;
-        PSFM_HIP(rocprim::radix_sort_pairs(c->sort_tmp.p, tmp_bytes, k_in, k_out, l_in, l_out, (size_t)n, 0u, end_bit, s));
-        c->fin_sort_form = 3;
+        int* l_out = c->sort_lanes.as<int>();
+        if ((st = c->sort_tmp.ensure(*scan_bytes)) != PSFM_OK) return st;
+        if (f.fmt.use32) st = psfm_sort_pairs32(c, c->sort_keys.as<unsigned>(), l_out, c->sort_keys.as<unsigned>() + n, l_out + n, n, f.end_bit, s);
+        else st = psfm_sort_pairs64(c, c->sort_keys.as<unsigned long long>(), l_out, c->sort_keys.as<unsigned long long>() + n, l_out + n, n, f.end_bit, s);
     }
+    if (st != PSFM_OK) return st;
+    c->fin_sort_form = f.sort_form;
+    return PSFM_OK;
+}
+
+// the pinned staging host_seg: at least `need` bytes (a new one gets `slack` more)
+static psfm_status psfm_host_seg_ensure(psfm_ctx* c, size_t need, size_t slack)
+{
+    if (c->host_seg_bytes >= need) return PSFM_OK;
+    if (c->host_seg) (void)hipHostFree(c->host_seg);
+    c->host_seg = nullptr; c->host_seg_bytes = 0;
+    PSFM_HIP(hipHostMalloc(&c->host_seg, need + slack, hipHostMallocDefault));
+    c->host_seg_bytes = need + slack;
+    return PSFM_OK;
+}
+
+// common tail: (key, lane) records already compacted to psfm_compact_dst() in the plan's key format
+static psfm_status psfm_finalize_sorted(psfm_ctx* c, const PsfmTrackDims& d, const PsfmFinForm& f, int64_t n, int64_t npts, bool delta_log,
+                                        hipStream_t s)
+{
+    psfm_status st;
+    size_t scan_bytes = 0;
+    if ((st = psfm_sort_records(c, f, n, &scan_bytes, s)) != PSFM_OK) return st;
     // birth / length / offset of every trajectory: from the group plan (few groups), else decode + scan over the trajectories
     if ((st = c->res_birth.ensure(sizeof(int) * n)) != PSFM_OK) return st;
     if ((st = c->res_len.ensure(sizeof(int) * n)) != PSFM_OK) return st;
     if ((st = c->res_off.ensure(sizeof(int64_t) * (n + 1))) != PSFM_OK) return st;
-    static const int plan_on = getenv("PSFM_FIN_PLAN") ? atoi(getenv("PSFM_FIN_PLAN")) : 1;      // 0: decode + scan always (A/B, tests)
-    const long long lmax = (long long)d.n_flows + 1;
-    const long long ng = lmax * (lmax + 1) / 2 + lmax + 1;      // group numbers last (last + 1) / 2 + birth, birth <= last <= lmax
+    const long long ng = f.ng;
+    const PsfmKeyFmt fmt = f.fmt;
     PsfmPlan pl;
     pl.gstart = nullptr; pl.goff = nullptr; pl.keys = (const void*)c->sort_keys.p; pl.use32 = fmt.use32; pl.shift_b = d.shift_b; pl.shift_d = d.shift_d;
     pl.birth_w = c->res_birth.as<int>(); pl.len_w = c->res_len.as<int>(); pl.off_w = c->res_off.as<int64_t>();
-    if (plan_on && ng <= PSFM_PLAN_MAX_GROUPS && n < (1ll << 31)) {
+    if (f.offsets_form == 1) {
         if ((st = c->scan_tmp.ensure((sizeof(int64_t) + sizeof(int)) * (size_t)ng)) != PSFM_OK) return st;
         int64_t* goff = c->scan_tmp.as<int64_t>();
         int* gstart = (int*)(goff + ng);
@@ -578,14 +506,8 @@ static psfm_status psfm_finalize_sorted(psfm_ctx* c, const PsfmTrackDims& d, int
     } else {
         c->fin_offsets_form = 3;
         if ((st = c->scan_tmp.ensure(sizeof(int64_t) * (n + 1))) != PSFM_OK) return st;
-        if (fmt.use32)
-            hipLaunchKernelGGL(psfm_decode32_kernel, dim3((unsigned)((n + 1 + PSFM_BLOCK - 1) / PSFM_BLOCK)), dim3(PSFM_BLOCK), 0, s,
-                               c->sort_keys.as<unsigned>(), n, d.shift_b, c->res_birth.as<int>(), c->res_len.as<int>(),
-                               c->scan_tmp.as<int64_t>());
-        else
-            hipLaunchKernelGGL(psfm_decode_kernel, dim3((unsigned)((n + 1 + PSFM_BLOCK - 1) / PSFM_BLOCK)), dim3(PSFM_BLOCK), 0, s,
-                               c->sort_keys.as<unsigned long long>(), n, d.shift_b, d.shift_d, c->res_birth.as<int>(),
-                               c->res_len.as<int>(), c->scan_tmp.as<int64_t>());
+        hipLaunchKernelGGL(psfm_decode_kernel, dim3((unsigned)((n + 1 + PSFM_BLOCK - 1) / PSFM_BLOCK)), dim3(PSFM_BLOCK), 0, s,
+                           (const void*)c->sort_keys.p, n, fmt, c->res_birth.as<int>(), c->res_len.as<int>(), c->scan_tmp.as<int64_t>());
         PSFM_HIP(hipGetLastError());
         PSFM_HIP(rocprim::exclusive_scan(c->sort_tmp.p, scan_bytes, c->scan_tmp.as<int64_t>(), c->res_off.as<int64_t>(),
                                          (int64_t)0, (size_t)(n + 1), rocprim::plus<int64_t>(), s));
@@ -622,15 +544,10 @@ psfm_status psfm_finalize(psfm_ctx* c, const PsfmTrackDims& d, hipStream_t s)
     PSFM_HIP(hipMemcpyAsync(hs, shards, sizeof(PsfmShard) * PSFM_NSHARD, hipMemcpyDeviceToHost, s));
     PSFM_HIP(hipStreamSynchronize(s));
     PsfmShardOffsets so;
+    int fin_cnt[PSFM_NSHARD];
     int64_t n = 0, npts = 0;
-    bool over = hc->overflow != 0;
-    for (int k = 0; k < PSFM_NSHARD; ++k) npts += hs[k].points;   // every log write was counted by its block
-    for (int k = 0; k < PSFM_NSHARD; ++k) {
-        if (hs[k].fin_cnt > d.shard_cap) over = true;
-        so.count[k] = hs[k].fin_cnt > d.shard_cap ? d.shard_cap : hs[k].fin_cnt;
-        so.start[k] = n;
-        n += so.count[k];
-    }
+    for (int k = 0; k < PSFM_NSHARD; ++k) { npts += hs[k].points; fin_cnt[k] = hs[k].fin_cnt; }   // every log write was counted by its block
+    const bool over = psfm_shard_offsets(fin_cnt, d.shard_cap, &so, &n) || hc->overflow != 0;
     if (over || hc->n_lanes > d.cap) {
         psfm_set_error("capacity exceeded: lanes used %d of %lld, trajectory records %lld of %lld (%d shards); "
                        "raise psfm_ctx_set_capacity", hc->n_lanes, (long long)d.cap, (long long)n,
@@ -644,15 +561,12 @@ psfm_status psfm_finalize(psfm_ctx* c, const PsfmTrackDims& d, hipStream_t s)
     psfm_status st;
     if ((st = c->sort_keys.ensure(sizeof(unsigned long long) * n * 2)) != PSFM_OK) return st;
     if ((st = c->sort_lanes.ensure(sizeof(int) * n * 2)) != PSFM_OK) return st;
-    unsigned end_bit_unused = 0;
-    const PsfmKeyFmt fmt = psfm_key_fmt(d, &end_bit_unused);
-    const int64_t half = psfm_records_in_first_half(d, n) ? 0 : n;
-    unsigned long long* kdst = fmt.use32 ? (unsigned long long*)(c->sort_keys.as<unsigned>() + half) : c->sort_keys.as<unsigned long long>() + half;
+    const PsfmFinForm f = psfm_form_of(d, n);
+    const PsfmFinDst dst = psfm_compact_dst(c, f, n);
     hipLaunchKernelGGL(psfm_compact_shards_kernel, dim3(64, PSFM_NSHARD), dim3(PSFM_BLOCK), 0, s,
-                       c->fin_keys.as<unsigned long long>(), c->fin_lanes.as<int>(), d.shard_cap, so,
-                       kdst, c->sort_lanes.as<int>() + half, fmt);
+                       c->fin_keys.as<unsigned long long>(), c->fin_lanes.as<int>(), d.shard_cap, so, dst.keys, dst.lanes, f.fmt);
     PSFM_HIP(hipGetLastError());
-    return psfm_finalize_sorted(c, d, n, npts, false, s);
+    return psfm_finalize_sorted(c, d, f, n, npts, false, s);
 }
 
 // ---- persistent frame loop: records sit in one private segment per block (+ a shared tail) ----
@@ -700,13 +614,8 @@ psfm_status psfm_finalize_persist(psfm_ctx* c, const PsfmTrackDims& d, bool* fal
 {
     *fallback = false;
     const int nseg = d.nblk + 1;
-    const size_t need = sizeof(int2) * (size_t)d.nblk;
-    if (c->host_seg_bytes < need) {
-        if (c->host_seg) (void)hipHostFree(c->host_seg);
-        c->host_seg = nullptr; c->host_seg_bytes = 0;
-        PSFM_HIP(hipHostMalloc(&c->host_seg, need, hipHostMallocDefault));
-        c->host_seg_bytes = need;
-    }
+    psfm_status st;
+    if ((st = psfm_host_seg_ensure(c, sizeof(int2) * (size_t)d.nblk, 0)) != PSFM_OK) return st;
     int2* hinfo = (int2*)c->host_seg;
     PsfmCounters* hc = (PsfmCounters*)c->host_pinned;
     PSFM_HIP(hipMemcpyAsync(hc, c->counters.p, sizeof(PsfmCounters), hipMemcpyDeviceToHost, s));
@@ -732,18 +641,15 @@ psfm_status psfm_finalize_persist(psfm_ctx* c, const PsfmTrackDims& d, bool* fal
     c->res_n_traj = n;
     c->res_n_points = 0;
     if (n == 0) return PSFM_OK;
-    psfm_status st;
     if ((st = c->sort_keys.ensure(sizeof(unsigned long long) * n * 2)) != PSFM_OK) return st;
     if ((st = c->sort_lanes.ensure(sizeof(int) * n * 2)) != PSFM_OK) return st;
-    unsigned end_bit_unused = 0;
-    const PsfmKeyFmt fmt = psfm_key_fmt(d, &end_bit_unused);
-    const int64_t half = psfm_records_in_first_half(d, n) ? 0 : n;
-    unsigned long long* kdst = fmt.use32 ? (unsigned long long*)(c->sort_keys.as<unsigned>() + half) : c->sort_keys.as<unsigned long long>() + half;
+    const PsfmFinForm f = psfm_form_of(d, n);
+    const PsfmFinDst dst = psfm_compact_dst(c, f, n);
     hipLaunchKernelGGL(psfm_compact_segments_kernel, dim3((unsigned)nseg), dim3(PSFM_BLOCK), 0, s,
                        c->fin_keys.as<unsigned long long>(), c->fin_lanes.as<int>(), (const int2*)c->seg_info.as<int2>(), d.nblk, d.seg_cap,
-                       (const PsfmCounters*)c->counters.as<PsfmCounters>(), d.spill_cap, kdst, c->sort_lanes.as<int>() + half, fmt);
+                       (const PsfmCounters*)c->counters.as<PsfmCounters>(), d.spill_cap, dst.keys, dst.lanes, f.fmt);
     PSFM_HIP(hipGetLastError());
-    return psfm_finalize_sorted(c, d, n, npts, true, s);   // the persistent loop logs flows, not positions
+    return psfm_finalize_sorted(c, d, f, n, npts, true, s);   // the persistent loop logs flows, not positions
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -792,7 +698,7 @@ __global__ __launch_bounds__(PSFM_WAVE) void psfm_batch_counts_kernel(const Psfm
     }
 }
 
-// combined key = (sequence << seq_shift) | key of the sequence (32- or 64-bit format, psfm_key_fmt)
+// combined key = (sequence << seq_shift) | key of the sequence (32- or 64-bit format: psfm_put_key)
 __global__ __launch_bounds__(PSFM_BLOCK) void psfm_compact_shards_batch_kernel(const PsfmFinSeq* __restrict__ T, unsigned long long* __restrict__ keys,
                                                                                int* __restrict__ lanes, PsfmKeyFmt fmt, int seq_shift)
 {
@@ -805,9 +711,7 @@ __global__ __launch_bounds__(PSFM_BLOCK) void psfm_compact_shards_batch_kernel(c
     for (int k = 0; k < shard; ++k) start += s_cnt[k];
     const int n = s_cnt[shard];
     for (int i = blockIdx.x * PSFM_BLOCK + threadIdx.x; i < n; i += gridDim.x * PSFM_BLOCK) {
-        const unsigned long long k = q.fin_keys[(int64_t)shard * q.shard_cap + i];
-        if (fmt.use32) ((unsigned*)keys)[start + i] = psfm_key32(k, fmt) | (seq_shift < 32 ? (unsigned)seq << seq_shift : 0u);
-        else keys[start + i] = k | ((unsigned long long)seq << seq_shift);
+        psfm_put_key(keys, start + i, q.fin_keys[(int64_t)shard * q.shard_cap + i], fmt, seq, seq_shift);
         lanes[start + i] = q.fin_lanes[(int64_t)shard * q.shard_cap + i];
     }
 }
@@ -819,23 +723,10 @@ __global__ __launch_bounds__(PSFM_BLOCK) void psfm_decode_batch_kernel(const Psf
     const int64_t i = (int64_t)blockIdx.x * PSFM_BLOCK + threadIdx.x;
     if (i > n) return;
     if (i == n) { len64[i] = 0; return; }
-    int seq, b, last;
-    if (fmt.use32) {
-        const unsigned k = ((const unsigned*)keys)[i];
-        seq = seq_shift < 32 ? (int)(k >> seq_shift) : 0;       // (a batch of one sequence whose key fills the word)
-        const unsigned tri = (seq_shift < 32 ? k & ((1u << seq_shift) - 1u) : k) >> fmt.shift_b;
-        int l = (int)((sqrtf(8.0f * (float)tri + 1.0f) - 1.0f) * 0.5f);      // (as psfm_decode32_kernel)
-        while (l > 0 && (unsigned)l * (unsigned)(l + 1) / 2u > tri) --l;
-        while ((unsigned)(l + 1) * (unsigned)(l + 2) / 2u <= tri) ++l;
-        last = l;
-        b = (int)(tri - (unsigned)l * (unsigned)(l + 1) / 2u);
-    } else {
-        const unsigned long long kk = ((const unsigned long long*)keys)[i];
-        seq = (int)(kk >> seq_shift);
-        const unsigned long long k = kk & ((1ull << seq_shift) - 1ull);
-        last = (int)(k >> fmt.shift_d);
-        b = (int)((k >> fmt.shift_b) & ((1ull << (fmt.shift_d - fmt.shift_b)) - 1ull));
-    }
+    int seq, last, b, idx;
+    const unsigned long long k = psfm_batch_split(psfm_key_at(keys, i, fmt.use32), fmt.use32, seq_shift, &seq);
+    if (fmt.use32) psfm_key32_fields((unsigned)k, fmt.shift_b, &last, &b, &idx);
+    else psfm_key64_fields(k, fmt.shift_b, fmt.shift_d, &last, &b, &idx);
     const PsfmFinSeq& q = T[seq];
     const int64_t local = i - q.rec_start;
     q.res_birth[local] = b;
@@ -866,13 +757,7 @@ psfm_status psfm_finalize_batch(psfm_ctx* own, psfm_ctx* const* ctxs, const Psfm
     psfm_status st;
     // the table: device copy in the owner's batch workspace behind the frame loop's table, host copy in its pinned staging
     const size_t tbytes = sizeof(PsfmFinSeq) * (size_t)n_seq, cbytes = sizeof(long long) * 4 * (size_t)n_seq;
-    const size_t need_host = tbytes + cbytes;
-    if (own->host_seg_bytes < need_host) {
-        if (own->host_seg) (void)hipHostFree(own->host_seg);
-        own->host_seg = nullptr; own->host_seg_bytes = 0;
-        PSFM_HIP(hipHostMalloc(&own->host_seg, need_host + 4096, hipHostMallocDefault));
-        own->host_seg_bytes = need_host + 4096;
-    }
+    if ((st = psfm_host_seg_ensure(own, tbytes + cbytes, 4096)) != PSFM_OK) return st;
     if ((st = own->seg_table.ensure(tbytes + cbytes)) != PSFM_OK) return st;
     PsfmFinSeq* hT = (PsfmFinSeq*)own->host_seg;
     long long* hcnt = (long long*)((char*)own->host_seg + tbytes);
@@ -931,61 +816,23 @@ psfm_status psfm_finalize_batch(psfm_ctx* own, psfm_ctx* const* ctxs, const Psfm
         return PSFM_OK;
     }
     // 3. the combined (sequence : key, lane) array, sorted once
-    unsigned end_bit = 0;
-    PsfmKeyFmt fmt = psfm_key_fmt(dk, &end_bit);
-    int seq_bits = 0;
-    while ((1 << seq_bits) < n_seq) ++seq_bits;
-    if (fmt.use32 && (int)end_bit + seq_bits > 32) {        // the sequence number does not fit beside a 32-bit key: 64-bit keys
-        fmt.use32 = 0;
-        int tbits = 1;
-        while ((1ll << tbits) < (long long)dk.n_flows + 2) ++tbits;
-        end_bit = (unsigned)(dk.shift_d + tbits);
-    }
-    if (!fmt.use32 && (int)end_bit + seq_bits > 64) { psfm_set_error("psfm_finalize_batch: key does not fit 64 bits"); return PSFM_ERR_ARG; }
-    const int seq_shift = (int)end_bit;
-    const unsigned sort_end = end_bit + (unsigned)seq_bits;
+    const PsfmFinForm f = psfm_form_of(dk, N, n_seq);      // (64-bit keys where the sequence number does not fit beside a 32-bit one)
+    if (!f.ok) { psfm_set_error("psfm_finalize_batch: key does not fit 64 bits"); return PSFM_ERR_ARG; }
     if ((st = own->sort_keys.ensure(sizeof(unsigned long long) * (size_t)N * 2)) != PSFM_OK) return st;
     if ((st = own->sort_lanes.ensure(sizeof(int) * (size_t)N * 2)) != PSFM_OK) return st;
     if ((st = own->scan_tmp.ensure(sizeof(int64_t) * (size_t)(N + 1) * 2)) != PSFM_OK) return st;
-    // (this file's sort ends in the first half whatever its pass count: with an even count the records start there)
-    const bool own_sort = psfm_own_sort(fmt, N);
-    const int64_t half = (own_sort && psfm_own_sort_passes(fmt, sort_end) % 2 == 0) ? 0 : N;
-    unsigned long long* kdst = fmt.use32 ? (unsigned long long*)(own->sort_keys.as<unsigned>() + half) : own->sort_keys.as<unsigned long long>() + half;
-    hipLaunchKernelGGL(psfm_compact_shards_batch_kernel, dim3(8, PSFM_NSHARD, (unsigned)n_seq), dim3(PSFM_BLOCK), 0, s, dT, kdst,
-                       own->sort_lanes.as<int>() + half, fmt, seq_shift);
+    const PsfmFinDst dst = psfm_compact_dst(own, f, N);
+    hipLaunchKernelGGL(psfm_compact_shards_batch_kernel, dim3(8, PSFM_NSHARD, (unsigned)n_seq), dim3(PSFM_BLOCK), 0, s, dT, dst.keys,
+                       dst.lanes, f.fmt, f.seq_shift);
     PSFM_HIP(hipGetLastError());
-    int* l_in = own->sort_lanes.as<int>() + N;
-    int* l_out = own->sort_lanes.as<int>();
-    size_t tmp_bytes = 0, scan_bytes = 0;
-    PSFM_HIP(rocprim::exclusive_scan(nullptr, scan_bytes, (int64_t*)nullptr, (int64_t*)nullptr, (int64_t)0, (size_t)(N + 1),
-                                     rocprim::plus<int64_t>(), s));
-    own->fin_sort_form = 0; own->fin_offsets_form = 0;
-    if (own_sort) {
-        if ((st = own->sort_tmp.ensure(scan_bytes)) != PSFM_OK) return st;      // (before the sort's launches: growing the buffer frees it)
-        if (fmt.use32) st = psfm_sort_pairs32(own, own->sort_keys.as<unsigned>(), l_out, own->sort_keys.as<unsigned>() + N, l_in, N, sort_end, s);
-        else st = psfm_sort_pairs64(own, own->sort_keys.as<unsigned long long>(), l_out, own->sort_keys.as<unsigned long long>() + N, l_in, N, sort_end, s);
-        if (st != PSFM_OK) return st;
-        own->fin_sort_form = fmt.use32 ? 1 : 2;
-    } else if (fmt.use32) {
-        unsigned* k_in = own->sort_keys.as<unsigned>() + N;
-        unsigned* k_out = own->sort_keys.as<unsigned>();
-        PSFM_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, k_in, k_out, l_in, l_out, (size_t)N, 0u, sort_end, s));
-        if ((st = own->sort_tmp.ensure(tmp_bytes > scan_bytes ? tmp_bytes : scan_bytes)) != PSFM_OK) return st;
-        PSFM_HIP(rocprim::radix_sort_pairs(own->sort_tmp.p, tmp_bytes, k_in, k_out, l_in, l_out, (size_t)N, 0u, sort_end, s));
-    } else {
-        unsigned long long* k_in = own->sort_keys.as<unsigned long long>() + N;
-        unsigned long long* k_out = own->sort_keys.as<unsigned long long>();
-        PSFM_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, k_in, k_out, l_in, l_out, (size_t)N, 0u, sort_end, s));
-        if ((st = own->sort_tmp.ensure(tmp_bytes > scan_bytes ? tmp_bytes : scan_bytes)) != PSFM_OK) return st;
-        PSFM_HIP(rocprim::radix_sort_pairs(own->sort_tmp.p, tmp_bytes, k_in, k_out, l_in, l_out, (size_t)N, 0u, sort_end, s));
-    }
-    if (!own_sort) own->fin_sort_form = 3;
-    own->fin_offsets_form = 3;
+    size_t scan_bytes = 0;
+    if ((st = psfm_sort_records(own, f, N, &scan_bytes, s)) != PSFM_OK) return st;
+    own->fin_offsets_form = f.offsets_form;
     // 4. decode -> per-sequence birth / length, combined lengths -> ONE scan -> per-sequence offsets; 5. the transpose gather
     int64_t* len64 = own->scan_tmp.as<int64_t>();
     int64_t* scan = len64 + (N + 1);
     hipLaunchKernelGGL(psfm_decode_batch_kernel, dim3((unsigned)((N + 1 + PSFM_BLOCK - 1) / PSFM_BLOCK)), dim3(PSFM_BLOCK), 0, s, dT,
-                       (const void*)own->sort_keys.p, N, fmt, seq_shift, len64);
+                       (const void*)own->sort_keys.p, N, f.fmt, f.seq_shift, len64);
     PSFM_HIP(hipGetLastError());
     PSFM_HIP(rocprim::exclusive_scan(own->sort_tmp.p, scan_bytes, len64, scan, (int64_t)0, (size_t)(N + 1), rocprim::plus<int64_t>(), s));
     hipLaunchKernelGGL(psfm_offsets_batch_kernel, dim3((unsigned)((n_max + 1 + PSFM_BLOCK - 1) / PSFM_BLOCK), (unsigned)n_seq), dim3(PSFM_BLOCK), 0, s,

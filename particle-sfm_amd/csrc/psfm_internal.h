@@ -164,7 +164,8 @@ struct psfm_ctx {
     PsfmBuf sort_keys, sort_lanes, sort_tmp, scan_tmp;
     PsfmBuf fin_marks;            // finalize: first sorted record of every (last, birth) group; all -1 between two calls (fin_marks_clean)
     bool fin_marks_clean = false;
-    int fin_sort_form = 0, fin_offsets_form = 0;   // what the last finalize ran (psfm_ctx_get_finalize_forms)
+    int fin_sort_form = 0, fin_offsets_form = 0;   // what the last finalize ran: sort_form / offsets_form of its plan (psfm_fin_form,
+                                                   // psfm_finalize_plan.h), 0 until that step was reached (psfm_ctx_get_finalize_forms)
     PsfmBuf res_birth, res_len, res_off, res_xy;
     int64_t res_n_traj = 0, res_n_points = 0;
     int res_n_flows = 0;           // flows of the sequence the result came from (psfm_result_keys checks its packed key)
@@ -335,9 +336,9 @@ int psfm_persist_guests(void);   // LDS-resident extra lanes per block
 psfm_status psfm_launch_chain_persist(psfm_ctx* c, const PsfmTrackDims& d, const float* flows, const uint8_t* occ,
                                       int64_t occ_pitch, const float* flows_b, float thres, hipStream_t s);
 
-// ---- finalize (psfm_finalize.hip) -----------------------------------------------------------
+// ---- finalize (psfm_finalize.hip; its decisions and key codec: psfm_finalize_plan.h) ---------
 psfm_status psfm_finalize(psfm_ctx* c, const PsfmTrackDims& d, hipStream_t s);
-// psfm_sort.hip: stable LSD radix sort of (32-bit key, int) pairs for the finalize (input in half0 when the pass count is even, else half1; result in half0)
+// psfm_sort.hip: stable LSD radix sort of (32-bit key, int) pairs for the finalize (input in half0 when the pass count is even, else half1 -- PsfmFinForm::first_half; result in half0)
 int psfm_sort_pairs32_passes(unsigned end_bit);
 int psfm_sort_pairs64_passes(unsigned end_bit);
 psfm_status psfm_sort_pairs64(psfm_ctx* c, unsigned long long* k_half0, int* v_half0, unsigned long long* k_half1, int* v_half1, int64_t n, unsigned end_bit, hipStream_t s);
