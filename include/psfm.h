@@ -92,7 +92,8 @@ typedef struct psfm_track_info {
     int32_t n_solves;
     int32_t chain_mode;        /* how the frame recurrence ran: 1 one launch per frame, 2 one persistent launch, 3 one launch per
                                   frame for a whole batch of sequences (psfm_connect_batch), 4 one launch per direction over
-                                  caller-given query points (psfm_track_queries) */
+                                  caller-given query points (psfm_track_queries), 5 one loop of launches over frames for query points
+                                  with the path-consistency solve (psfm_track_queries_optimize) */
 } psfm_track_info;
 
 const char* psfm_last_error(void);
@@ -274,10 +275,43 @@ psfm_status psfm_connect(psfm_ctx* ctx, const float* flows_f, const float* flows
  * info->chain_mode = 4 -- and every consumer of a result works on it unchanged (psfm_result_device / _copy, psfm_result_filter /
  * _filtered_copy, psfm_window_sample, psfm_traj_to_matches, the label merge), except psfm_result_keys, whose key needs a birth grid
  * index: it refuses a query result (PSFM_ERR_ARG).  Identical calls give identical bytes.  Synchronises `stream`.
- * Out of scope: path consistency for query tracks, tracking through occlusion, several sequences per call. */
+ * Out of scope: tracking through occlusion, several sequences per call.  (Path consistency: psfm_track_queries_optimize.) */
 psfm_status psfm_track_queries(psfm_ctx* ctx, const float* flows_f, const uint8_t* occ_f, const float* flows_b, const uint8_t* occ_b,
                                int n_flows, int h, int w, const double* q_xy, const int32_t* q_t, int64_t n_q,
                                psfm_track_info* info_host, void* stream);
+
+/* psfm_track_queries WITH the stride-2 path-consistency solve every grid trajectory of track_optimize gets (track_optimize.py:49-50):
+ * the reference's IncrementalTrajectorySet(buffer_size=3) fed with the queries of every frame (new_traj_all takes any points), then
+ * the body of track_optimize.py:37-50.  Forward, for f = 0 .. n_flows-1:
+ *   1. the queries with q_t == f become active (a query with q_t == n_flows never steps: length 1);
+ *   2. every active query steps from its tail p_f exactly as in psfm_track_queries (motion-boundary form included); one that is not
+ *      alive ends at its last position, one that is alive gets p_{f+1};
+ *   3. if f >= 1, the active queries that now hold three positions p_{f-1}, p_f, p_{f+1} (alive, f + 1 - q_t >= 2) are the rows of ONE
+ *      joint solve, built as optimize_buffer does (trajectory.py:161-194): flow01 = grid_sample(flows[f-1], p0),
+ *      flow02 = grid_sample(flows_f2[f-1], p0), occ02 = grid_sample(occ_f2[f-1], p0), scale = (1 - occ02) * (|flow02| < 20) in fp32,
+ *      ref1 = p0 + flow01, ref2 = p0 + flow02, uv12 = (p1, p2), cost map flows[f].  The result overwrites p_f and p_{f+1}; the next
+ *      step starts from the optimised p_{f+1};
+ *   4. at the end of the stack every active query ends.
+ * The solve of a frame is JOINT over the call's queries -- Ceres' trust-region loop is global, as it is over the reference's active
+ * set -- so a query's positions depend on its companions exactly as a grid track's do; rows are in query order.  A frame with no row
+ * runs no solve (the reference's np.stack([]) raises there: the one deviation, on input the reference cannot handle).  The query point
+ * itself (p0 of its first solve) is never moved.
+ * Backward: the same engine on the time-reversed sequence -- the stride-1 stack is flows_b with ITS maps occ_b = flow_check(flows_b,
+ * flows_f); the stride-2 stack is flows_b2 (flows_b2[f]: frame f+2 -> f) with ITS maps occ_b2 = flow_check(flows_b2, flows_f2).
+ * Both: the halves are solved independently and joined as psfm_track_queries joins them.
+ *   flows_f, occ_f, flows_f2 (n_flows-1,H,W,2), occ_f2 (n_flows-1,H,W)   the forward direction: all four, or none
+ *   flows_b, occ_b, flows_b2, occ_b2                                      the backward direction: all four, or none
+ * With n_flows == 1 no solve can happen and the stride-2 pointers may be NULL.  Refusals as psfm_track_queries (PSFM_ERR_ARG before
+ * anything is tracked, the previous result intact, psfm_last_error() names the first bad query), and a direction whose stride-1
+ * stack comes without its stride-2 stack while n_flows >= 2.  The result replaces the context's result set as psfm_track_queries'
+ * does (trajectory i is query i, info->n_traj = n_q, a live label merge is void, psfm_result_keys refuses it); info->chain_mode = 5.
+ * psfm_result_solve_stats: one entry per solve that ran, forward frames ascending, then backward frames in the order they ran
+ * (descending).  The solve is the one psfm_optimize_location runs and honours psfm_ctx_set_solver / psfm_ctx_set_resident_budget as
+ * it does.  One small device-to-host copy per frame (the row count).  Synchronises `stream`. */
+psfm_status psfm_track_queries_optimize(psfm_ctx* ctx, const float* flows_f, const uint8_t* occ_f, const float* flows_f2,
+                                        const uint8_t* occ_f2, const float* flows_b, const uint8_t* occ_b, const float* flows_b2,
+                                        const uint8_t* occ_b2, int n_flows, int h, int w, const double* q_xy, const int32_t* q_t,
+                                        int64_t n_q, psfm_track_info* info_host, void* stream);
 
 /* The loop of the reference's driver over a directory of sequences (run_particlesfm.py:168-176 -> connect_point_trajectory ->
  * main_connect_point_trajectories.py:36-53 per sequence) for n_seq sequences of the SAME frame size and sample ratio (any

@@ -172,6 +172,7 @@ struct psfm_ctx {
     bool res_is_query = false;     // the result is psfm_track_queries': trajectory i is query i, no birth grid index (psfm_result_keys
                                    // refuses it); cleared by every other entry point that replaces the result
     PsfmBuf qr_ws;                 // psfm_track_queries (psfm_query.hip): first refused query | lengths per direction | scan storage
+                                   // (psfm_track_queries_optimize, psfm_query_pc.hip: ... | rows per wave | the rows of a frame's solve)
     // solver workspace
     PsfmBuf sol_x, sol_state, sol_partials, sol_ctrl, sol_misc, sol_stats, sol_fused, sol_bar;
     PsfmBuf sol_list;              // launch chain / resident solve: per block, the lanes that take part in the solve (pc_build_list)
@@ -292,6 +293,14 @@ psfm_status psfm_launch_motion_boundary(const float* flows, const uint8_t* occ, 
 // psfm_launch_chain_step with the motion-boundary verdict: `kill` is the frame's kill map
 psfm_status psfm_launch_chain_step_mb(psfm_ctx* c, const PsfmTrackDims& d, const float* flow, const uint8_t* kill, int frame, bool optimize,
                                       hipStream_t s);
+
+// ---- query results (psfm_query.hip), shared by psfm_track_queries and psfm_track_queries_optimize (psfm_query_pc.hip) ----------
+// PSFM_ERR_ARG naming the first query with a non-finite coordinate or a frame outside [0, n_flows] (first_bad: 8 bytes on the device)
+psfm_status psfm_query_refuse(psfm_ctx* c, const char* who, const double* q_xy, const int32_t* q_t, unsigned Q, int n_flows,
+                              unsigned long long* first_bad, hipStream_t s);
+// births, lengths, offsets and the CSR of Q > 0 queries from the position slab in c->log and the directions' lengths (NULL: not tracked)
+psfm_status psfm_query_finish(psfm_ctx* c, const int32_t* q_t, const int* len_f, const int* len_b, unsigned Q, int n_flows, int64_t* bsum,
+                              int64_t* n_points, hipStream_t s);
 
 // ---- batch: B same-shape sequences per launch (psfm_batch.hip; kernels beside their single-sequence forms) --------------------
 #define PSFM_BATCH_MAX 64

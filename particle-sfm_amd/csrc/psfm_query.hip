@@ -129,6 +129,53 @@ __global__ __launch_bounds__(PSFM_QUERY_BLOCK) void psfm_query_gather_kernel(con
         if ((f >= b) & (f < e)) out[o + (f - b)] = psfm_ld(slab + (size_t)f * Q, q * 16u);
 }
 
+// first query with a non-finite coordinate or a frame outside [0, n_flows]: PSFM_ERR_ARG naming it (`who`: the entry point), else PSFM_OK
+psfm_status psfm_query_refuse(psfm_ctx* c, const char* who, const double* q_xy, const int32_t* q_t, unsigned Q, int n_flows,
+                              unsigned long long* first_bad, hipStream_t s)
+{
+    if (Q == 0) return PSFM_OK;
+    unsigned long long* hq = (unsigned long long*)((char*)c->host_pinned + 448);
+    const unsigned nblk = (Q + PSFM_QUERY_BLOCK - 1) / PSFM_QUERY_BLOCK;
+    PSFM_HIP(hipMemsetAsync(first_bad, 0xff, sizeof(unsigned long long), s));
+    hipLaunchKernelGGL(psfm_query_validate_kernel, dim3(nblk), dim3(PSFM_QUERY_BLOCK), 0, s, (const double2*)q_xy, q_t, Q, n_flows, first_bad);
+    PSFM_HIP(hipGetLastError());
+    PSFM_HIP(hipMemcpyAsync(&hq[0], first_bad, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    PSFM_HIP(hipStreamSynchronize(s));
+    if (hq[0] != ~0ull) {
+        psfm_set_error("%s: query %llu has a non-finite coordinate or a frame outside [0, %d]", who, hq[0], n_flows);
+        return PSFM_ERR_ARG;
+    }
+    return PSFM_OK;
+}
+
+// The finish of a query result (Q > 0): births and lengths from the directions' lengths (NULL: not tracked), offsets, the slab's rows
+// (c->log) gathered into the CSR; *n_points: its points.  bsum: (blocks + 1) i64 of scan storage.  Synchronises s.
+psfm_status psfm_query_finish(psfm_ctx* c, const int32_t* q_t, const int* len_f, const int* len_b, unsigned Q, int n_flows, int64_t* bsum,
+                              int64_t* n_points, hipStream_t s)
+{
+    psfm_status st;
+    unsigned long long* hq = (unsigned long long*)((char*)c->host_pinned + 448);
+    const unsigned nblk = (Q + PSFM_QUERY_BLOCK - 1) / PSFM_QUERY_BLOCK;
+    c->prof.begin(PSFM_PROF_FINALIZE, s);                       // lengths -> offsets -> CSR as the finalize
+    hipLaunchKernelGGL(psfm_query_plan_kernel, dim3(nblk), dim3(PSFM_QUERY_BLOCK), 0, s, q_t, len_f, len_b, Q,
+                       c->res_birth.as<int>(), c->res_len.as<int>(), c->res_off.as<int64_t>(), bsum);
+    hipLaunchKernelGGL(psfm_query_scan_kernel, dim3(1), dim3(PSFM_QUERY_BLOCK), 0, s, bsum, nblk, Q, c->res_off.as<int64_t>());
+    hipLaunchKernelGGL(psfm_query_offsets_kernel, dim3(nblk), dim3(PSFM_QUERY_BLOCK), 0, s, (const int64_t*)bsum, Q, c->res_off.as<int64_t>());
+    PSFM_HIP(hipGetLastError());
+    PSFM_HIP(hipMemcpyAsync(&hq[1], c->res_off.as<int64_t>() + Q, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    PSFM_HIP(hipStreamSynchronize(s));
+    const int64_t npts = (int64_t)hq[1];
+    if ((st = c->res_xy.ensure(sizeof(double2) * (size_t)(npts > 0 ? npts : 1))) != PSFM_OK) return st;
+    hipLaunchKernelGGL(psfm_query_gather_kernel, dim3(nblk), dim3(PSFM_QUERY_BLOCK), 0, s, c->log.as<double2>(), c->res_birth.as<int>(),
+                       c->res_len.as<int>(), c->res_off.as<int64_t>(), Q, n_flows, c->res_xy.as<double2>());
+    c->prof.end(s);
+    PSFM_HIP(hipGetLastError());
+    PSFM_HIP(hipStreamSynchronize(s));
+    c->prof.collect();
+    *n_points = npts;
+    return PSFM_OK;
+}
+
 template <bool BACK>
 static void psfm_launch_query_track(const PsfmQueryArgs& a, bool mb, hipStream_t s)
 {
@@ -163,7 +210,6 @@ extern "C" psfm_status psfm_track_queries(psfm_ctx* c, const float* flows_f, con
     const unsigned Q = (unsigned)n_q;
     const size_t P = (size_t)h * w;
     const unsigned nblk = (Q + PSFM_QUERY_BLOCK - 1) / PSFM_QUERY_BLOCK;
-    unsigned long long* hq = (unsigned long long*)((char*)c->host_pinned + 448);      // [0] first refused query, [1] points of the result
 
     // ---- workspace: first refused query | len_f | len_b | block totals of the length scan ----
     const size_t o_lenf = 64, o_lenb = o_lenf + (((size_t)Q * 4 + 63) & ~(size_t)63), o_bsum = o_lenb + (((size_t)Q * 4 + 63) & ~(size_t)63);
@@ -172,17 +218,7 @@ extern "C" psfm_status psfm_track_queries(psfm_ctx* c, const float* flows_f, con
     unsigned long long* first_bad = (unsigned long long*)ws;
 
     // ---- refusals: a non-finite coordinate, a frame outside [0, n_flows] -- before anything is tracked ----
-    if (Q > 0) {
-        PSFM_HIP(hipMemsetAsync(first_bad, 0xff, sizeof(unsigned long long), s));
-        hipLaunchKernelGGL(psfm_query_validate_kernel, dim3(nblk), dim3(PSFM_QUERY_BLOCK), 0, s, (const double2*)q_xy, q_t, Q, n_flows, first_bad);
-        PSFM_HIP(hipGetLastError());
-        PSFM_HIP(hipMemcpyAsync(&hq[0], first_bad, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-        PSFM_HIP(hipStreamSynchronize(s));
-        if (hq[0] != ~0ull) {
-            psfm_set_error("psfm_track_queries: query %llu has a non-finite coordinate or a frame outside [0, %d]", hq[0], n_flows);
-            return PSFM_ERR_ARG;
-        }
-    }
+    if ((st = psfm_query_refuse(c, "psfm_track_queries", q_xy, q_t, Q, n_flows, first_bad, s)) != PSFM_OK) return st;
 
     // ---- from here on the call replaces the result (and the lane tables of an unfinished sharded run: the slab lives in the log) ----
     psfm_shard_abandon(c);
@@ -234,23 +270,8 @@ extern "C" psfm_status psfm_track_queries(psfm_ctx* c, const float* flows_f, con
         }
         c->prof.end(s);
         PSFM_HIP(hipGetLastError());
-        c->prof.begin(PSFM_PROF_FINALIZE, s);                   // ... lengths -> offsets -> CSR as the finalize
-        int64_t* bsum = (int64_t*)(ws + o_bsum);
-        hipLaunchKernelGGL(psfm_query_plan_kernel, dim3(nblk), dim3(PSFM_QUERY_BLOCK), 0, s, q_t, (const int*)len_f, (const int*)len_b, Q,
-                           c->res_birth.as<int>(), c->res_len.as<int>(), c->res_off.as<int64_t>(), bsum);
-        hipLaunchKernelGGL(psfm_query_scan_kernel, dim3(1), dim3(PSFM_QUERY_BLOCK), 0, s, bsum, nblk, Q, c->res_off.as<int64_t>());
-        hipLaunchKernelGGL(psfm_query_offsets_kernel, dim3(nblk), dim3(PSFM_QUERY_BLOCK), 0, s, (const int64_t*)bsum, Q, c->res_off.as<int64_t>());
-        PSFM_HIP(hipGetLastError());
-        PSFM_HIP(hipMemcpyAsync(&hq[1], c->res_off.as<int64_t>() + Q, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-        PSFM_HIP(hipStreamSynchronize(s));
-        const int64_t npts = (int64_t)hq[1];
-        if ((st = c->res_xy.ensure(sizeof(double2) * (size_t)(npts > 0 ? npts : 1))) != PSFM_OK) return st;
-        hipLaunchKernelGGL(psfm_query_gather_kernel, dim3(nblk), dim3(PSFM_QUERY_BLOCK), 0, s, c->log.as<double2>(), c->res_birth.as<int>(),
-                           c->res_len.as<int>(), c->res_off.as<int64_t>(), Q, n_flows, c->res_xy.as<double2>());
-        c->prof.end(s);
-        PSFM_HIP(hipGetLastError());
-        PSFM_HIP(hipStreamSynchronize(s));
-        c->prof.collect();
+        int64_t npts = 0;
+        if ((st = psfm_query_finish(c, q_t, len_f, len_b, Q, n_flows, (int64_t*)(ws + o_bsum), &npts, s)) != PSFM_OK) return st;
         c->res_n_traj = (int64_t)Q;
         c->res_n_points = npts;
     }

@@ -35,7 +35,7 @@ EXPORTS = [
     "psfm_sparse_depth_last_ms", "psfm_colmap_points3d_count", "psfm_colmap_points3d_scan",
     "psfm_ctx_set_motion_boundary", "psfm_motion_boundary", "psfm_kill_map",
     "psfm_depth_display", "psfm_ctx_set_depth_display", "psfm_depth_display_last_ms", "psfm_depth_display_chunk",
-    "psfm_track_queries",
+    "psfm_track_queries", "psfm_track_queries_optimize",
 ]
 
 
@@ -100,6 +100,7 @@ def lib():
     L.psfm_connect_batch.argtypes = [ctypes.POINTER(vp), i32, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp),
                                      ctypes.POINTER(i32), i32, i32, f32, i32, ctypes.POINTER(TrackInfo), vp]
     L.psfm_track_queries.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, i64, ctypes.POINTER(TrackInfo), vp]
+    L.psfm_track_queries_optimize.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, i64, ctypes.POINTER(TrackInfo), vp]
     L.psfm_result_device.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp)]
     L.psfm_result_copy.argtypes = [vp, vp, vp, vp, vp, vp]
     L.psfm_result_solve_stats.argtypes = [vp, ctypes.POINTER(SolveStats), i32, ctypes.POINTER(ctypes.c_int32)]

@@ -427,7 +427,8 @@ def run_track(flows, occ_maps, flows_f2, occ_maps_s2, sample_ratio, return_devic
     return _result_to_host(ctx, info)
 
 
-def run_track_queries(xy, t, flows=None, occ=None, flows_b=None, occ_b=None, motion_boundary=False, mb_thres=0.02, return_device=False):
+def run_track_queries(xy, t, flows=None, occ=None, flows_b=None, occ_b=None, motion_boundary=False, mb_thres=0.02, return_device=False,
+                      flows_f2=None, occ_f2=None, flows_b2=None, occ_b2=None):
     """Caller-given query points tracked through a flow stack in ONE psfm_track_queries call: query i is the position xy[i] ((Q,2)
     float64) at frame t[i] ((Q,) int, 0 <= t <= n_flows); per query the body of track.py:37-47 (grid_sample + step_forward) until the
     first step that is not alive or the end of the stack.
@@ -435,11 +436,19 @@ def run_track_queries(xy, t, flows=None, occ=None, flows_b=None, occ_b=None, mot
     f+1 -> f) and ITS occlusion maps, flow_check(flows_b, flows).  One stack: tracked that way; both: both ways, one trajectory.
     Returns a TrajectoryList whose trajectory i is query i (length >= 1); the result also replaces the context's result set, so the
     consumers of a tracking result (result_to_trajectory_set, sample_window_device, match_tables_device ...) work on it.
-    A non-finite coordinate or a frame outside [0, n_flows] raises PsfmError (status PSFM_ERR_ARG) naming the first such query."""
+    A non-finite coordinate or a frame outside [0, n_flows] raises PsfmError (status PSFM_ERR_ARG) naming the first such query.
+    flows_f2 / occ_f2 (forward) and flows_b2 / occ_b2 (backward; flows_b2[f]: frame f+2 -> f, occ_b2 = flow_check(flows_b2, flows_f2)):
+    the stride-2 stacks (n-1,H,W,2) and THEIR occlusion maps (n-1,H,W).  With any of them given ONE psfm_track_queries_optimize call
+    runs instead: after every step the queries that hold three positions are corrected by the stride-2 path-consistency solve of
+    track_optimize.py:49-50, jointly over the call's queries (a query's positions then depend on its companions, as a grid track's
+    do); a frame with no such query runs no solve.  R.info["chain_mode"] is 5 and R.info["n_solves"] counts the solves.  Without them
+    the call is exactly psfm_track_queries."""
     import torch
     ctx = _hip.context()
     dev = torch.device("cuda", ctx.device)
     fl = oc = fb = ob = None
+    stride2 = {"flows_f2": flows_f2, "occ_f2": occ_f2, "flows_b2": flows_b2, "occ_b2": occ_b2}
+    optimize = any(v is not None for v in stride2.values())
     if flows is not None:
         fl = _as_device_stack(flows, torch.float32, (1, 1, 2))
     if occ is not None:
@@ -456,6 +465,17 @@ def run_track_queries(xy, t, flows=None, occ=None, flows_b=None, occ_b=None, mot
         for name, m, tail in (("flows", fl, (H, W, 2)), ("occ", oc, (H, W)), ("flows_b", fb, (H, W, 2)), ("occ_b", ob, (H, W))):
             if m is not None and (int(m.shape[0]) != n or tuple(m.shape[1:]) != tail):
                 raise ValueError("track_queries: %s has shape %s, expected %s" % (name, tuple(m.shape), (n,) + tail))
+    s2 = {}
+    for name, m in stride2.items():
+        if m is None:
+            s2[name] = None
+            continue
+        flow = name.startswith("flows")
+        m = _as_device_stack(m, torch.float32 if flow else torch.uint8, (1, 1, 2) if flow else (1, 1))
+        tail = (H, W, 2) if flow else (H, W)
+        if ref is not None and (int(m.shape[0]) != n - 1 or (m.numel() > 0 and tuple(m.shape[1:]) != tail)):
+            raise ValueError("track_queries: %s has shape %s, expected %s" % (name, tuple(m.shape), (n - 1,) + tail))
+        s2[name] = m if m.numel() > 0 else None       # (one flow: no solve can happen, the library takes NULL)
 
     def as_t(a, dt):
         a = a.detach() if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
@@ -466,18 +486,28 @@ def run_track_queries(xy, t, flows=None, occ=None, flows_b=None, occ_b=None, mot
         raise ValueError("track_queries: %d positions for %d frames" % (q_xy.shape[0], q_t.shape[0]))
     info = _hip.TrackInfo()
     with _MotionBoundary(ctx, motion_boundary, mb_thres):
-        st = _hip.lib().psfm_track_queries(ctx.handle, _hip.ptr(fl), _hip.ptr(oc), _hip.ptr(fb), _hip.ptr(ob), n, H, W, _hip.ptr(q_xy),
-                                           _hip.ptr(q_t), int(q_xy.shape[0]), ctypes.byref(info), _hip.current_stream_ptr(ctx.device))
+        if optimize:
+            st = _hip.lib().psfm_track_queries_optimize(ctx.handle, _hip.ptr(fl), _hip.ptr(oc), _hip.ptr(s2["flows_f2"]), _hip.ptr(s2["occ_f2"]),
+                                                        _hip.ptr(fb), _hip.ptr(ob), _hip.ptr(s2["flows_b2"]), _hip.ptr(s2["occ_b2"]), n, H, W,
+                                                        _hip.ptr(q_xy), _hip.ptr(q_t), int(q_xy.shape[0]), ctypes.byref(info),
+                                                        _hip.current_stream_ptr(ctx.device))
+        else:
+            st = _hip.lib().psfm_track_queries(ctx.handle, _hip.ptr(fl), _hip.ptr(oc), _hip.ptr(fb), _hip.ptr(ob), n, H, W, _hip.ptr(q_xy),
+                                               _hip.ptr(q_t), int(q_xy.shape[0]), ctypes.byref(info), _hip.current_stream_ptr(ctx.device))
     _hip.check(st)
     if return_device:
         return info
     return _result_to_host(ctx, info)
 
 
-def run_connect_queries(xy, t, flows_f, flows_b, thres=1.0, direction="forward", motion_boundary=False, mb_thres=0.02, return_device=False):
+def run_connect_queries(xy, t, flows_f, flows_b, thres=1.0, direction="forward", motion_boundary=False, mb_thres=0.02, return_device=False,
+                        flows_f2=None, flows_b2=None):
     """flow_check + run_track_queries: the occlusion maps each direction needs come from flow_check_device in that direction's own
     orientation -- forward: flow_check(flows_f, flows_b); backward: flow_check(flows_b, flows_f).  direction: "forward", "backward"
-    or "both".  flows_f, flows_b: (n,H,W,2) stacks, flows_b[f] being the flow from frame f+1 to frame f."""
+    or "both".  flows_f, flows_b: (n,H,W,2) stacks, flows_b[f] being the flow from frame f+1 to frame f.
+    flows_f2, flows_b2 (both, (n-1,H,W,2), flows_b2[f]: frame f+2 -> f): the query tracks get the stride-2 path-consistency solve
+    (run_track_queries); each direction's stride-2 maps are flow_check_device in that direction's orientation -- forward:
+    flow_check(flows_f2, flows_b2); backward: flow_check(flows_b2, flows_f2)."""
     import torch
     from .utils import flow_check_device
     if direction not in ("forward", "backward", "both"):
@@ -487,8 +517,20 @@ def run_connect_queries(xy, t, flows_f, flows_b, thres=1.0, direction="forward",
     n = min(int(ff.shape[0]), int(fb.shape[0]))
     ff, fb = ff[:n], fb[:n]
     kw = {}
+    if (flows_f2 is None) != (flows_b2 is None):
+        raise ValueError("connect_queries: the stride-2 maps of either direction need both stride-2 stacks")
+    f2 = b2 = None
+    if flows_f2 is not None:
+        f2 = _as_device_stack(flows_f2, torch.float32, (1, 1, 2))[:max(n - 1, 0)]
+        b2 = _as_device_stack(flows_b2, torch.float32, (1, 1, 2))[:max(n - 1, 0)]
+        if int(f2.shape[0]) != n - 1 or int(b2.shape[0]) != n - 1:
+            raise ValueError("connect_queries: need %d stride-2 flows per direction" % (n - 1))
     if direction in ("forward", "both"):
         kw.update(flows=ff, occ=flow_check_device(ff, fb, thres)[1])
+        if f2 is not None:
+            kw.update(flows_f2=f2, occ_f2=flow_check_device(f2, b2, thres)[1] if n > 1 else f2.new_zeros((0,) + tuple(ff.shape[1:3]), dtype=torch.uint8))
     if direction in ("backward", "both"):
         kw.update(flows_b=fb, occ_b=flow_check_device(fb, ff, thres)[1])
+        if f2 is not None:
+            kw.update(flows_b2=b2, occ_b2=flow_check_device(b2, f2, thres)[1] if n > 1 else f2.new_zeros((0,) + tuple(ff.shape[1:3]), dtype=torch.uint8))
     return run_track_queries(xy, t, motion_boundary=motion_boundary, mb_thres=mb_thres, return_device=return_device, **kw)
