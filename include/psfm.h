@@ -232,6 +232,12 @@ psfm_status psfm_sort_records64(psfm_ctx* ctx, uint64_t* keys, int32_t* values, 
  * Reads host-side state only; either pointer may be NULL. */
 psfm_status psfm_ctx_get_finalize_forms(psfm_ctx* ctx, int* sort_form, int* offsets_form);
 
+/* Whether the LAST id assignment of this context ran the placed form: after the persistent frame loop, with 32-bit sort keys and
+ * n_flows + 1 <= 256, the records are placed by birth order (which the loop knows) and sorted in ONE pass on the last valid time
+ * instead of being compacted and sorted in four (csrc/psfm_place.h; PSFM_FIN_PLACE=0 in the environment keeps the four passes).
+ * sort_form above reports 1 either way; the bytes of the result are the same.  *placed: 0 / 1.  Reads host-side state only. */
+psfm_status psfm_ctx_get_finalize_placed(psfm_ctx* ctx, int* placed);
+
 /* track.py:24-50 when flows_f2 == NULL, track_optimize.py:24-53 otherwise.
  *   flows    (n_flows,H,W,2) f32      occ     (n_flows,H,W) u8
  *   flows_f2 (n_flows-1,H,W,2) f32    occ_s2  (n_flows-1,H,W) u8        (stride-2 stacks)

@@ -177,7 +177,7 @@ extern "C" psfm_status psfm_ctx_destroy(psfm_ctx* c)
                        &c->occupied, &c->counters, &c->shards, &c->survivors, &c->sort_keys, &c->sort_lanes, &c->sort_tmp,
                        &c->scan_tmp, &c->fin_marks, &c->res_birth, &c->res_len, &c->res_off, &c->res_xy, &c->sol_x, &c->sol_state,
                        &c->sol_partials, &c->sol_ctrl, &c->sol_misc, &c->sol_stats, &c->sol_fused, &c->sol_bar, &c->sol_list, &c->occ_own, &c->occ2_own,
-                       &c->handoff, &c->seg_info, &c->seg_table, &c->persist_bar, &c->batch_tab, &c->batch_ws, &c->batch_fc, &c->win_ws, &c->flt_ids, &c->flt_birth, &c->flt_len, &c->flt_off, &c->flt_xy,
+                       &c->handoff, &c->place_tab, &c->seg_info, &c->seg_table, &c->persist_bar, &c->batch_tab, &c->batch_ws, &c->batch_fc, &c->win_ws, &c->flt_ids, &c->flt_birth, &c->flt_len, &c->flt_off, &c->flt_xy,
                        &c->mt_kp_off, &c->mt_q, &c->mt_pts, &c->mt_kp_ind, &c->mt_kp_xy, &c->mt_moff, &c->mt_keys, &c->mt_rows, &c->mt_gid, &c->mt_pairs,
                        &c->lb_state, &c->lb_first, &c->lb_flag, &c->lb_ws, &c->lb_ids, &c->lb_off, &c->lb_frames, &c->lb_xy, &c->lb_labels, &c->gt_flag, &c->kill,
                        &c->db_kp, &c->db_pairs, &c->db_rows, &c->db_ws, &c->sd_ws, &c->dd_ws, &c->dd_comp, &c->qr_ws};
@@ -404,6 +404,13 @@ extern "C" psfm_status psfm_ctx_get_finalize_forms(psfm_ctx* c, int* sort_form, 
     return PSFM_OK;
 }
 
+extern "C" psfm_status psfm_ctx_get_finalize_placed(psfm_ctx* c, int* placed)
+{
+    PSFM_CHECK_CTX(c);
+    if (placed) *placed = c->fin_placed;
+    return PSFM_OK;
+}
+
 // Sizes of one run of the frame recurrence.  g_own < 0: the whole stride-r grid; otherwise the number of grid points whose
 // births this process owns (track-sharded runs): lane / record tables are sized for those, keys for the whole grid.
 psfm_status psfm_track_dims(psfm_ctx* c, int n_flows, int h, int w, int ratio, int64_t g_own, PsfmTrackDims& d)
@@ -538,6 +545,7 @@ static psfm_status psfm_track_impl(psfm_ctx* c, const float* flows, const uint8_
             if ((st = c->handoff.ensure((size_t)dp.nblk * 256 * 24)) != PSFM_OK) return st;
             if ((st = c->seg_info.ensure(sizeof(int) * 2 * (size_t)dp.nblk)) != PSFM_OK) return st;
             if ((st = c->persist_bar.ensure((size_t)(4 * PSFM_NSHARD + 1) * 128)) != PSFM_OK) return st;
+            if ((st = c->place_tab.ensure(psfm_place_table_bytes(dp))) != PSFM_OK) return st;
             if (pipe && (st = pipe->need(n_flows - 1, false, s)) != PSFM_OK) return st;   // every occlusion map
             bool fallback = false;
             {

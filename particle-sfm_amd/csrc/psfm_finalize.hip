@@ -13,6 +13,8 @@
 //
 // What a call DECIDES (key width, sort bits, which sort, which half of sort_keys the compaction fills, group plan or decode + scan) is
 // psfm_fin_form() of psfm_finalize_plan.h, computed once by each entry point; that header also holds the only code that takes a key apart.
+// After the persistent loop one more decision follows from it, psfm_place_form() of psfm_place.h: the records are PLACED by birth order
+// (the loop leaves the order behind) and one pass on `last` finishes the sort -- psfm_place.hip instead of the compaction and the four passes.
 #include <cstring>
 #include <stdio.h>
 #include <rocprim/device/device_radix_sort.hpp>
@@ -21,6 +23,7 @@
 #include "psfm_device.h"
 #include "psfm_finalize_plan.h"
 #include "psfm_internal.h"
+#include "psfm_place.h"
 
 #define PSFM_BLOCK 256
 
@@ -438,13 +441,18 @@ static psfm_status psfm_rocprim_sort(psfm_ctx* c, int64_t n, unsigned end_bit, s
 
 // Sorts the n compacted records (psfm_compact_dst) by the plan's key bits into the first halves of sort_keys / sort_lanes.  sort_tmp is
 // sized for the offset scan over n + 1 entries as well (*scan_bytes), BEFORE the sort's launches: growing the buffer frees it.
-static psfm_status psfm_sort_records(psfm_ctx* c, const PsfmFinForm& f, int64_t n, size_t* scan_bytes, hipStream_t s)
+// placed: the records sit in the second halves in birth order (psfm_place_records) and ONE pass on `last` sorts them (psfm_place.h).
+static psfm_status psfm_sort_records(psfm_ctx* c, const PsfmFinForm& f, int64_t n, size_t* scan_bytes, hipStream_t s, bool placed = false)
 {
     psfm_status st;
     PSFM_HIP(rocprim::exclusive_scan(nullptr, *scan_bytes, (int64_t*)nullptr, (int64_t*)nullptr, (int64_t)0,
                                      (size_t)(n + 1), rocprim::plus<int64_t>(), s));
-    c->fin_sort_form = 0; c->fin_offsets_form = 0;
-    if (f.sort_form == 3) {
+    c->fin_sort_form = 0; c->fin_offsets_form = 0; c->fin_placed = 0;
+    if (placed) {
+        int* l_out = c->sort_lanes.as<int>();
+        if ((st = c->sort_tmp.ensure(*scan_bytes)) != PSFM_OK) return st;
+        st = psfm_place_sort(c, c->sort_keys.as<unsigned>(), l_out, c->sort_keys.as<unsigned>() + n, l_out + n, n, s);
+    } else if (f.sort_form == 3) {
         st = f.fmt.use32 ? psfm_rocprim_sort<unsigned>(c, n, f.end_bit, *scan_bytes, s) : psfm_rocprim_sort<unsigned long long>(c, n, f.end_bit, *scan_bytes, s);
     } else {
         int* l_out = c->sort_lanes.as<int>();
@@ -454,6 +462,7 @@ static psfm_status psfm_sort_records(psfm_ctx* c, const PsfmFinForm& f, int64_t 
     }
     if (st != PSFM_OK) return st;
     c->fin_sort_form = f.sort_form;
+    c->fin_placed = placed ? 1 : 0;
     return PSFM_OK;
 }
 
@@ -470,11 +479,11 @@ static psfm_status psfm_host_seg_ensure(psfm_ctx* c, size_t need, size_t slack)
 
 // common tail: (key, lane) records already compacted to psfm_compact_dst() in the plan's key format
 static psfm_status psfm_finalize_sorted(psfm_ctx* c, const PsfmTrackDims& d, const PsfmFinForm& f, int64_t n, int64_t npts, bool delta_log,
-                                        hipStream_t s)
+                                        hipStream_t s, bool placed = false)
 {
     psfm_status st;
     size_t scan_bytes = 0;
-    if ((st = psfm_sort_records(c, f, n, &scan_bytes, s)) != PSFM_OK) return st;
+    if ((st = psfm_sort_records(c, f, n, &scan_bytes, s, placed)) != PSFM_OK) return st;
     // birth / length / offset of every trajectory: from the group plan (few groups), else decode + scan over the trajectories
     if ((st = c->res_birth.ensure(sizeof(int) * n)) != PSFM_OK) return st;
     if ((st = c->res_len.ensure(sizeof(int) * n)) != PSFM_OK) return st;
@@ -644,6 +653,12 @@ psfm_status psfm_finalize_persist(psfm_ctx* c, const PsfmTrackDims& d, bool* fal
     if ((st = c->sort_keys.ensure(sizeof(unsigned long long) * n * 2)) != PSFM_OK) return st;
     if ((st = c->sort_lanes.ensure(sizeof(int) * n * 2)) != PSFM_OK) return st;
     const PsfmFinForm f = psfm_form_of(d, n);
+    // placed form (psfm_place.h): scan + placement by birth order instead of the compaction, one pass instead of the sort's four
+    static const int place_on = getenv("PSFM_FIN_PLACE") ? atoi(getenv("PSFM_FIN_PLACE")) : 1;      // 0: compaction + the sort's own passes (A/B, tests)
+    if (psfm_place_form(1, f, d.n_flows, n, d.cap, place_on)) {
+        if ((st = psfm_place_records(c, d, f, n, s)) != PSFM_OK) return st;
+        return psfm_finalize_sorted(c, d, f, n, npts, true, s, true);
+    }
     const PsfmFinDst dst = psfm_compact_dst(c, f, n);
     hipLaunchKernelGGL(psfm_compact_segments_kernel, dim3((unsigned)nseg), dim3(PSFM_BLOCK), 0, s,
                        c->fin_keys.as<unsigned long long>(), c->fin_lanes.as<int>(), (const int2*)c->seg_info.as<int2>(), d.nblk, d.seg_cap,

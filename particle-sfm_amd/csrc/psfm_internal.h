@@ -153,6 +153,7 @@ struct psfm_ctx {
     PsfmBuf seg_info;     // per block: records in its private segment, trajectory points it wrote
     PsfmBuf seg_table;    // finalize: (src start, count, dst start) per record segment
     PsfmBuf persist_bar;  // barrier: 64 arrival counters, 1 top counter, 64 release flags (128 B apart)
+    PsfmBuf place_tab;    // birth masks per (frame, 64 grid points) as the loop leaves them | births of the virtual blocks as starts inside the frame | births per frame (psfm_place.h)
     int persist_max_blocks = -1;   // resident 256-thread blocks on this device (-1: not queried yet)
     int chain_mode = 0;            // 0 auto, 1 per-frame launches only, 2 persistent loop required
     bool mb_enable = false;        // psfm_ctx_set_motion_boundary: tracks also die on motion boundaries (per-frame launches only)
@@ -166,6 +167,7 @@ struct psfm_ctx {
     bool fin_marks_clean = false;
     int fin_sort_form = 0, fin_offsets_form = 0;   // what the last finalize ran: sort_form / offsets_form of its plan (psfm_fin_form,
                                                    // psfm_finalize_plan.h), 0 until that step was reached (psfm_ctx_get_finalize_forms)
+    int fin_placed = 0;                            // ... and whether its records were placed by birth order and sorted in one pass (psfm_place.h)
     PsfmBuf res_birth, res_len, res_off, res_xy;
     int64_t res_n_traj = 0, res_n_points = 0;
     int res_n_flows = 0;           // flows of the sequence the result came from (psfm_result_keys checks its packed key)
@@ -354,6 +356,13 @@ psfm_status psfm_sort_pairs64(psfm_ctx* c, unsigned long long* k_half0, int* v_h
 psfm_status psfm_sort_pairs32(psfm_ctx* c, unsigned* k_half0, int* v_half0, unsigned* k_half1, int* v_half1, int64_t n, unsigned end_bit, hipStream_t s);
 // after psfm_launch_chain_persist; *fallback = true (and PSFM_OK): the loop gave up, rerun with per-frame launches
 psfm_status psfm_finalize_persist(psfm_ctx* c, const PsfmTrackDims& d, bool* fallback, hipStream_t s);
+// psfm_place.hip: the placed form of that finalize (psfm_place.h).  The loop's birth masks and what the scan makes of them live in
+// c->place_tab (psfm_place_table_bytes, allocated in front of the loop's launch); psfm_place_records fills the second halves of
+// sort_keys / sort_lanes in birth order, psfm_place_sort is the one stable pass on `last` from the second halves into the first
+struct PsfmFinForm;
+size_t psfm_place_table_bytes(const PsfmTrackDims& d);
+psfm_status psfm_place_records(psfm_ctx* c, const PsfmTrackDims& d, const PsfmFinForm& f, int64_t n, hipStream_t s);
+psfm_status psfm_place_sort(psfm_ctx* c, unsigned* k_half0, int* v_half0, const unsigned* k_half1, const int* v_half1, int64_t n, hipStream_t s);
 
 // ---- solver (psfm_solver.hip: launch chain, resident solve, host driver; fused / frame / device-paced forms: psfm_solver_fused.hip) ----
 // In-place solve on the trajectory log for frame index f (positions at f-1, f, f+1): enqueue `unroll`

@@ -28,13 +28,27 @@
 // 524288 threads on an MI355X).
 // The results (ids, lengths, positions) do not depend on which lane hosts which track: ids derive from the key
 // (last valid time, birth frame, birth grid index) at finalize.
+//
+// Birth order.  The finalize places the records by (birth frame, rank among that frame's births in grid order) and then sorts them
+// in one pass (psfm_place.h).  The loop knows that order -- thread L owns grid point L, virtual blocks are in grid order -- and leaves
+// it behind as ONE store per wave and frame: lane 0 stores the wave's ballot of births of frame t >= 1 into bmask[t][L >> 6] (64
+// consecutive grid points per word, four words per virtual block).  Every word of the rows 1 .. n_flows - 1 is stored in every call by
+// the wave that owns its grid points, a zero where nothing is born, so the table is never cleared and nothing of an earlier call is
+// left in it; frame 0 is implied (every grid point is born there).  Nothing of it lives across frames.  Where the store sits was
+// measured (profiles/EXPERIMENTS.md 24): what it costs the loop is not the store but the scalar round trip to the argument block
+// in front of it -- a count per block stored by thread 0 in the phase-2 section plus every newborn's ordinal stored into a free
+// slot of the log: +23 to +31 us per 100-frame sequence; the mask stored where the ballot is formed: +17 to +22; behind the phase-2
+// passes with a kernarg site of its own: +10 to +35; at the frame's last kernarg site with every field of that site loaded in one
+// round trip (where it is now): +7 to +9 at the median of two sittings.
 #include <hip/hip_ext.h>
 #include <stdlib.h>
 
 #include "psfm_internal.h"
 #include "psfm_chain.h"
+#include "psfm_place.h"
 
 #define PP_BLOCK 256
+static_assert(PP_BLOCK == PSFM_PLACE_VB, "psfm_place.h takes a virtual block of the loop for 256 grid points");
 #define PP_NW (PP_BLOCK / PSFM_WAVE)
 #define PP_PROBE 8
 #ifndef PP_PRE_WAVES
@@ -82,6 +96,9 @@
 #endif
 #define PP_POOLED (-1)
 #define PP_PEND (-2)
+#define PP_BORN (1 << 30)  // in a frame's `npts`: this thread's grid point respawned in the frame.  The flag rides in a register that is live
+                         // across the phase-2 passes anyway, to where the birth mask is stored (the ballot itself held that far would be two
+                         // more scalars across the passes)
 #define PP_DIED (-3)     // between its own step and section C of the same frame: the track died in THIS frame's step (PP_PEND from C on).
                          // (A `live` flag held across E and the barrier instead was a 64-bit lane mask in two scalar registers.)
 
@@ -113,6 +130,7 @@ struct PsfmPersistArgs {
     int n_flows;
     int nblk;                                  // gridDim.x (read from here: the implicit-argument pointer would be one more 64-bit value held across the loop)
     PsfmFastDiv gwdiv, rdiv;                   // (rdiv: generic ratio only)
+    unsigned long long* bmask; int bm_words;   // birth masks ("Birth order" above): row t of bm_words words, word = 64 consecutive grid points
 };
 #define PP_SURV ((2 * PSFM_NSHARD + 1) * 32)   // first survivor word, in words from `bar`
 
@@ -508,6 +526,7 @@ __global__ __launch_bounds__(PP_BLOCK) PP_WAVES void psfm_chain_persist_kernel(P
         const bool pend = bf == PP_PEND;
         if (bf == PP_DIED) bf = PP_PEND;
         const unsigned long long bm = __ballot(birth), am = __ballot(adopted), pm = __ballot(pend);
+        if (birth) npts |= PP_BORN;      // (for the birth mask stored behind the phase-2 passes)
         if (lane == 0) { s_births[wave] = __popcll(bm); s_adopt[wave] = __popcll(am); s_pend[wave] = __popcll(pm); }
         if (birth) s_new_g[wave * PSFM_WAVE + psfm_rank_in(bm)] = L;
         if (adopted) s_ad_tid[wave * PSFM_WAVE + psfm_rank_in(am)] = tid;
@@ -745,7 +764,7 @@ __global__ __launch_bounds__(PP_BLOCK) PP_WAVES void psfm_chain_persist_kernel(P
         }
         PP_TL(5);
         asm volatile("" : "+s"(t), "+v"(tid));   // (t & 1, t - 1, tid == 0 below: from t and tid, not held across the passes)
-        if (npts) s_npts[tid] += npts;
+        if (npts & ~PP_BORN) s_npts[tid] += npts & ~PP_BORN;
         const unsigned long long alm = __ballot(any_alive);
         if (lane == 0 && alm != 0ull) s_alive_any[t & 1] = 1;   // benign race: every writer stores 1
         __syncthreads();
@@ -767,9 +786,24 @@ __global__ __launch_bounds__(PP_BLOCK) PP_WAVES void psfm_chain_persist_kernel(P
         // ---- F: everything this block wrote is acknowledged -> arrive ----
         // (a step samples the occlusion map of its frame as early as right after the previous arrival, when only the
         // barrier before that one is known to be complete: maps up to t+2 must be finished before arriving at #t+1)
-        if (PA->fc) {
-            const int nf = PA->n_flows, need = t + 3 < nf ? t + 3 : nf;
-            if (!(PP_WHATIF & 16)) for (; fc_next < need; ++fc_next) psfm_fc_slice(fc_next, tid);
+        {
+            // (everything this site needs of the argument block is loaded up front, in ONE scalar round trip: the birth mask's fields
+            // behind a round trip of their own -- wherever in the frame -- cost the loop 10-35 us per sequence, EXPERIMENTS 24)
+            const PsfmHotPtr a = psfm_hot();
+            const int fc = a->fc, nf = a->n_flows;
+#ifndef PP_NO_BIRTH_MASKS      // (measurement builds: the loop without the store, to be run with PSFM_FIN_PLACE=0 only)
+            {   // birth order: this wave's births of the frame as one 64-bit word, for the finalize ("Birth order" above)
+                const int gw = a->bm_words, per = a->xcd_per, b = PP_BID;
+                unsigned long long* bmask = a->bmask;
+                const unsigned long long born = __ballot((npts & PP_BORN) != 0);
+                const int word = ((per > 0 && b < 8 * per) ? (b & 7) * per + (b >> 3) : b) * (PP_BLOCK / PSFM_WAVE) + (tid / PSFM_WAVE);   // (psfm_vblock)
+                if ((tid & (PSFM_WAVE - 1)) == 0 && t > 0 && word < gw) bmask[(size_t)t * gw + word] = born;
+            }
+#endif
+            if (fc) {
+                const int need = t + 3 < nf ? t + 3 : nf;
+                if (!(PP_WHATIF & 16)) for (; fc_next < need; ++fc_next) psfm_fc_slice(fc_next, tid);
+            }
         }
         // ---- F: arrive.  No block barrier in front of it: a wave whose stores are acknowledged counts itself in (LDS) and
         //      goes on to the next frame; the wave that comes last arrives for the block ----
@@ -907,6 +941,7 @@ psfm_status psfm_launch_chain_persist(psfm_ctx* c, const PsfmTrackDims& d, const
     k.fin_keys = c->fin_keys.as<unsigned long long>(); k.fin_lanes = c->fin_lanes.as<int>();
     k.seg_cap = d.seg_cap; k.spill_base = d.nblk * d.seg_cap; k.spill_cap = d.spill_cap;
     k.seg_info = c->seg_info.as<int2>();
+    a.bmask = c->place_tab.as<unsigned long long>(); a.bm_words = psfm_place_words(d.G);
     a.bar = c->persist_bar.as<unsigned>();
     a.n_flows = d.n_flows; a.nblk = d.nblk; k.shift_b = d.shift_b; k.shift_d = d.shift_d;
     a.gwdiv = psfm_fastdiv_make((unsigned)d.GW); a.rdiv = psfm_fastdiv_make((unsigned)d.ratio);

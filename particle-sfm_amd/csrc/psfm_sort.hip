@@ -13,8 +13,10 @@
 //                 in front of b -- the group rows (64 in flight at once, behind the tile's own loads) + the tile's own prefix
 //                 row; ranks by wave-wide digit matching (8 ballots per round, an LDS counter row per wave: no LDS atomics);
 //                 the tile is put in order in LDS and leaves as runs of equal digits
-//   Two launches per pass, no atomics on global memory, no fills, nothing to zero between passes: 5.7 + 17.6 us per pass at
-//   the headline shape (four passes 93 us) against rocPRIM's 45.  Measured on the way (profiles/r06/r06_v_*,
+//   Two launches per pass, no atomics on global memory, no fills, nothing to zero between passes: on the headline's records the
+//   four passes are 37 us of H + 70 us of S = 107 us of kernels in 8 launches, against 180 us in 14 for rocPRIM's sort (4 passes
+//   of 29.7 + a 15.7 us histogram + 9 fills of 5.1: profiles/EXPERIMENTS.md 8.6).  After the persistent loop with at most 255 flows
+//   only ONE pass is left, and it is psfm_place.hip's (the records arrive in birth order).  Measured on the way (profiles/r06/r06_v_*,
 //   scripts/micro/sort_whatif.sh): every tile adding its counts to group rows and totals with global adds (130 k adds on
 //   4 352 addresses) made H a 19-us kernel; one block per tile + the group step by the block that finishes last in its group
 //   (write-through rows, a ticket, L2-bypassing loads) put a 9-us tail on H, 42 us with release / acquire fences in it (a

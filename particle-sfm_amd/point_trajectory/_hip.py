@@ -23,7 +23,7 @@ EXPORTS = [
     "psfm_shard_solve_writeback", "psfm_shard_solve_record", "psfm_shard_finish", "psfm_result_keys",
     "psfm_shard_solve_control_async", "psfm_shard_window_state", "psfm_shard_peek_stall", "psfm_shard_frame",
     "psfm_shard_solve_control_chain_async", "psfm_shard_solve_poll", "psfm_shard_solve_local", "psfm_shard_solve_redo_local", "psfm_connect_batch", "psfm_solver_launches", "psfm_ctx_set_resident_budget", "psfm_resident_capacity", "psfm_load_flo_stack",
-    "psfm_path_consistency_eval", "psfm_sort_records", "psfm_sort_records64", "psfm_ctx_get_finalize_forms",
+    "psfm_path_consistency_eval", "psfm_sort_records", "psfm_sort_records64", "psfm_ctx_get_finalize_forms", "psfm_ctx_get_finalize_placed",
     "psfm_shard_peer_area", "psfm_shard_peer_epoch", "psfm_shard_peer_open", "psfm_shard_peer_connect", "psfm_shard_solve_blocks", "psfm_shard_solve_peer",
     "psfm_labels_begin", "psfm_labels_merge_window", "psfm_labels_finish", "psfm_labels_device", "psfm_labels_copy", "psfm_labels_to_matches",
     "psfm_traj_augment", "psfm_traj_encode_weight_count", "psfm_traj_encode",
@@ -95,6 +95,7 @@ def lib():
     L.psfm_sort_records.argtypes = [vp, vp, vp, i64, i32, vp]
     L.psfm_sort_records64.argtypes = [vp, vp, vp, i64, i32, vp]
     L.psfm_ctx_get_finalize_forms.argtypes = [vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]
+    L.psfm_ctx_get_finalize_placed.argtypes = [vp, ctypes.POINTER(ctypes.c_int32)]
     L.psfm_track.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, ctypes.POINTER(TrackInfo), vp]
     L.psfm_connect.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, vp, vp, ctypes.POINTER(TrackInfo), vp]
     L.psfm_connect_batch.argtypes = [ctypes.POINTER(vp), i32, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp),
@@ -246,6 +247,13 @@ class Context:
         a, b = ctypes.c_int32(), ctypes.c_int32()
         check(lib().psfm_ctx_get_finalize_forms(self._h, ctypes.byref(a), ctypes.byref(b)))
         return {"sort": int(a.value), "offsets": int(b.value)}
+
+    def finalize_placed(self):
+        """1 when the last id assignment of this context placed its records by birth order and sorted them in one pass (after the
+        persistent frame loop, 32-bit keys, at most 255 flows; PSFM_FIN_PLACE=0 turns it off), else 0.  Same bytes either way."""
+        a = ctypes.c_int32()
+        check(lib().psfm_ctx_get_finalize_placed(self._h, ctypes.byref(a)))
+        return int(a.value)
 
     def set_sparse_depth(self, budget_bytes=1 << 30, timing=False):
         """psfm_sfm.convert: bytes of depth maps + winner maps (12 per pixel) one psfm_sparse_depth call may take (0: no limit; one
