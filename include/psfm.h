@@ -467,6 +467,31 @@ size_t psfm_traj_decode_workspace_bytes(int64_t k);
 psfm_status psfm_traj_decode(psfm_ctx* ctx, const float* encoding, const float* weights, int64_t k, void* workspace,
                              size_t workspace_bytes, float* logits, float* prob, uint8_t* pred, void* stream);
 
+/* psfm_traj_decode for n_win windows (the windows of main_motion_segmentation.py:69-112, of one sequence or of several) in ONE
+ * sequence of launches: as many launches as ONE psfm_traj_decode, whatever n_win, the k[b] and the data are.  No new rule: for every
+ * window b, logits[b], prob[b] and pred[b] are BIT-IDENTICAL to psfm_traj_decode(encoding[b], k[b]) on that window alone -- the same
+ * 64-point tiles numbered inside the window, the same per-block partial sums added in the same fixed order, InstanceNorm and both
+ * softmaxes over the k[b] points of that window only.  No floating-point atomics; identical calls give identical bytes.
+ *   encoding  HOST array of n_win DEVICE pointers, encoding[b] = [16][k[b]] f32 (may be NULL where k[b] == 0)
+ *   k         HOST array of n_win counts; 0 (the window is skipped, its outputs are not touched) or 2 <= k[b] <= the single call's
+ *             cap (128 k[b] <= 2^31 - 1: the kernels' 32-bit indices are relative to a window's own buffers)
+ *   logits, prob, pred   HOST arrays of n_win DEVICE pointers ([k[b]] f32, f32, u8); an array, or a single entry, may be NULL
+ *   workspace psfm_traj_decode_batch_workspace_bytes(k, n_win) bytes on the DEVICE: the windows' psfm_traj_decode workspaces one
+ *             after another, each on a 256-byte boundary (the sum of psfm_traj_decode_workspace_bytes(k[b])); contents before
+ *             the call do not matter and are unspecified after.  Returns 0 for a batch the call refuses.
+ * The host arrays are read before the call returns; the per-window table (k, workspace offset, input, outputs, first tile, first
+ * slice) travels by value in the kernel arguments: nothing is uploaded, no staging buffer outlives the call.  The convolutions and
+ * the pooled product run over the tiles (slices) of all windows in one grid, the statistics and the softmax over the points on a
+ * (channel, window) grid, the OAFilter stack on [128][100] with one block per window.  ASYNCHRONOUS on `stream`: no allocation, no
+ * host synchronisation.  n_win == 0 or every k[b] == 0: PSFM_OK, nothing launched.  PSFM_ERR_ARG, nothing launched: n_win outside
+ * [0, 64] (callers split longer lists); a k[b] < 0, == 1 or above the cap (the message names the first such window); a NULL
+ * encoding[b] with k[b] > 0; NULL weights or workspace while any k[b] > 0; workspace_bytes too small (the message names the needed
+ * size). */
+size_t psfm_traj_decode_batch_workspace_bytes(const int64_t* k, int n_win);
+psfm_status psfm_traj_decode_batch(psfm_ctx* ctx, int n_win, const float* const* encoding, const int64_t* k, const float* weights,
+                                   void* workspace, size_t workspace_bytes, float* const* logits, float* const* prob,
+                                   uint8_t* const* pred, void* stream);
+
 /* sfm/matches_from_flow.py:51-118 (traj_to_matches) from the saved set that psfm_result_filter left in HBM -- the
  * reference's per-trajectory Python loops as index arithmetic on the device (no track.npy round trip):
  *   keypoints  image i lists the kept points observed in frame i in trajectory (id) order (:67-81); labels_dev: optional

@@ -2,6 +2,7 @@
 // workspace layout, the plan (which launch reads and writes what), the InstanceNorm / BatchNorm fold, the statistics combine, the
 // two softmaxes and the reduction orders, shared by the kernels (psfm_decoder.hip) and the host build of the CPU suite
 // (tests/host/decoder_host.cpp through tests/host/shim).
+// psfm_decoder_batch.h adds the window dimension of psfm_traj_decode_batch on top of this file.
 //
 // Reference: traj_oa_depth.decoder = OANBlock(128, 16, depth 8, clusters 100), eval mode (motion_seg/core/network/oanet.py:13-206),
 // then torch.sigmoid (traj_oa_depth.py:124) and `> 0.5` (main_motion_segmentation.py:80).  N = k trajectories are the points, B = 1.
@@ -150,16 +151,18 @@ struct PsfmDecPlan {
     double *stat_part, *sm_part;
 };
 
-// The fixed sequence of launches for k points.  `ws` is the workspace base, `w` the packed weights; nothing is dereferenced here.
-inline void psfm_dec_plan(PsfmDecPlan& P, const float* enc, const float* w, int64_t k, void* ws, float* logits, float* prob, uint8_t* pred)
+// Where the eleven sections of a workspace begin, in the order of PsfmDecWs.
+struct PsfmDecBufs { char *a, *t, *x1, *xup, *emb, *stat_part, *stat_fin, *sm_part, *sm_fin, *pool_part, *x2; };
+
+// The fixed sequence of launches on the sections B for input enc; `w` is the packed weights.  Nothing is dereferenced here, and
+// nothing depends on k: psfm_decoder_batch.h plans once with section NAMES in place of addresses and resolves them per window.
+inline void psfm_dec_plan_at(PsfmDecPlan& P, const float* enc, const float* w, const PsfmDecBufs& B, float* logits, float* prob, uint8_t* pred)
 {
-    const PsfmDecWs L = psfm_dec_workspace(k);
-    char* base = (char*)ws;
-    float *A = (float*)(base + L.a), *T = (float*)(base + L.t), *X1 = (float*)(base + L.x1), *XUP = (float*)(base + L.xup);
-    double* fin = (double*)(base + L.stat_fin);
-    P.nsteps = 0; P.nb = L.nb; P.nb2 = L.nb2; P.k = k; P.w = w;
-    P.x1 = X1; P.emb = (float*)(base + L.emb); P.sm_fin = (float*)(base + L.sm_fin); P.pool_part = (float*)(base + L.pool_part);
-    P.x2 = (float*)(base + L.x2); P.stat_part = (double*)(base + L.stat_part); P.sm_part = (double*)(base + L.sm_part);
+    float *A = (float*)B.a, *T = (float*)B.t, *X1 = (float*)B.x1, *XUP = (float*)B.xup;
+    double* fin = (double*)B.stat_fin;
+    P.nsteps = 0; P.w = w;
+    P.x1 = X1; P.emb = (float*)B.emb; P.sm_fin = (float*)B.sm_fin; P.pool_part = (float*)B.pool_part;
+    P.x2 = (float*)B.x2; P.stat_part = (double*)B.stat_part; P.sm_part = (double*)B.sm_part;
     int slot = 0;
     const PsfmDecSeg none = {0, 0, 0, 0, 0, 0, 0, 0};
     // a layer step, followed by the reduction of its statistics into a fresh slot (returned) unless it stores none
@@ -211,6 +214,17 @@ inline void psfm_dec_plan(PsfmDecPlan& P, const float* enc, const float* w, int6
     st = layer(PSFM_DEC_PLAIN, PSFM_DEC_C, 3, seg(T, pw + PSFM_DEC_PW_WB, 128, 128, st_t, pw + PSFM_DEC_PW_BN2, 128, 0),
                seg(X1, pw, 128, 256, 0, 0, 0, 0), seg(XUP, pw + 128, 128, 256, 0, 0, 0, 0), pw + PSFM_DEC_PW_BB, pw + PSFM_DEC_PW_SCB, 0, A);
     for (int i = 0; i < 3; i++) st = point_cn(w + PSFM_DEC_W_L1_2 + PSFM_DEC_PW_SIZE + i * PSFM_DEC_PC_SIZE, A, st, A, i == 2);
+}
+
+// The plan for k points in the workspace at `ws`.
+inline void psfm_dec_plan(PsfmDecPlan& P, const float* enc, const float* w, int64_t k, void* ws, float* logits, float* prob, uint8_t* pred)
+{
+    const PsfmDecWs L = psfm_dec_workspace(k);
+    char* base = (char*)ws;
+    const PsfmDecBufs B = {base + L.a, base + L.t, base + L.x1, base + L.xup, base + L.emb, base + L.stat_part, base + L.stat_fin,
+                           base + L.sm_part, base + L.sm_fin, base + L.pool_part, base + L.x2};
+    psfm_dec_plan_at(P, enc, w, B, logits, prob, pred);
+    P.nb = L.nb; P.nb2 = L.nb2; P.k = k;
 }
 
 // ---- arithmetic -------------------------------------------------------------------------------------------------------------

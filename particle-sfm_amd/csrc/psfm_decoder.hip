@@ -6,7 +6,9 @@
 // launch per convolution normalises its input while it stages it, forms the product on the exact fp32 matrix instruction
 // (v_mfma_f32_32x32x2_f32: bit for bit the k-ordered fmaf chain of psfm_decoder.h) and leaves its output's channel statistics as
 // per-block f64 partials.  What is not the matrix instruction -- the plan, the folds, the softmaxes, the orders -- is psfm_decoder.h.
-#include "psfm_decoder.h"
+// The five kernel bodies are __device__ functions; psfm_traj_decode's kernels call them with the block's own index, the kernels of
+// psfm_traj_decode_batch (the windows of a sequence in ONE sequence of launches, psfm_decoder_batch.h) after they found their window.
+#include "psfm_decoder_batch.h"
 #include "psfm_internal.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -51,15 +53,34 @@ __device__ __forceinline__ void pd_gemm(f32x16 (&acc)[NT], const float* __restri
     }
 }
 
-// One convolution over the points (psfm_decoder.h: PsfmDecLayer).  A block owns PSFM_DEC_TILE points and all output channels: wave
-// w holds rows 32 w .. 32 w + 31 of both 32-point tiles in 2 x 16 accumulator registers.
-__global__ __launch_bounds__(PSFM_DEC_THREADS) void psfm_dec_layer_kernel(const PsfmDecLayer Y, int k)
+// Where a block's addresses come from.  PdOne: the plan holds them (psfm_traj_decode).  PdWin: the plan holds section names and the
+// block resolves them in its window of the batch (psfm_decoder_batch.h); the three outputs come from the table.
+struct PdOne {
+    template <class T> __device__ __forceinline__ T* operator()(T* p) const { return p; }
+    __device__ __forceinline__ float* logits(const PsfmDecLayer& Y) const { return Y.logits; }
+    __device__ __forceinline__ float* prob(const PsfmDecLayer& Y) const { return Y.prob; }
+    __device__ __forceinline__ uint8_t* pred(const PsfmDecLayer& Y) const { return Y.pred; }
+};
+struct PdWin {
+    PsfmDecWin W;
+    float *lo, *pr;
+    uint8_t* pd;
+    template <class T> __device__ __forceinline__ T* operator()(T* name) const { return psfm_dec_resolve(name, W); }
+    __device__ __forceinline__ float* logits(const PsfmDecLayer&) const { return lo; }
+    __device__ __forceinline__ float* prob(const PsfmDecLayer&) const { return pr; }
+    __device__ __forceinline__ uint8_t* pred(const PsfmDecLayer&) const { return pd; }
+};
+
+// One convolution over the points (psfm_decoder.h: PsfmDecLayer), block `blk` of the k points.  A block owns PSFM_DEC_TILE points and
+// all output channels: wave w holds rows 32 w .. 32 w + 31 of both 32-point tiles in 2 x 16 accumulator registers.
+template <class R>
+__device__ __forceinline__ void pd_layer(const PsfmDecLayer& Y, const R& at, int k, int blk)
 {
     __shared__ float ldsX[PSFM_DEC_TILE * PSFM_DEC_LDX];
     __shared__ float ldsW[PSFM_DEC_C * PSFM_DEC_LDW];
     __shared__ float fm[PSFM_DEC_C], fs[PSFM_DEC_C], ft[PSFM_DEC_C];
     const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63, col = lane & 31;
-    const int p0 = (int)blockIdx.x * PSFM_DEC_TILE, np = min(PSFM_DEC_TILE, k - p0);
+    const int p0 = blk * PSFM_DEC_TILE, np = min(PSFM_DEC_TILE, k - p0);
     f32x16 acc[2];
 #pragma unroll
     for (int r = 0; r < 16; r++) {
@@ -68,16 +89,18 @@ __global__ __launch_bounds__(PSFM_DEC_THREADS) void psfm_dec_layer_kernel(const 
     }
     for (int si = 0; si < Y.nseg; si++) {
         const PsfmDecSeg& S = Y.seg[si];
+        const float* src = at(S.src);
+        const double* stat = at(S.stat);
         __syncthreads();                                    // the products of the segment before have read ldsX
-        if (S.stat)
-            for (int c = tid; c < S.cin; c += PSFM_DEC_THREADS) psfm_dec_fold(S.stat[c], S.stat[PSFM_DEC_C + c], S.bn, S.bn_n, S.bn_c0 + c, fm[c], fs[c], ft[c]);
+        if (stat)
+            for (int c = tid; c < S.cin; c += PSFM_DEC_THREADS) psfm_dec_fold(stat[c], stat[PSFM_DEC_C + c], S.bn, S.bn_n, S.bn_c0 + c, fm[c], fs[c], ft[c]);
         __syncthreads();
         for (int idx = tid; idx < S.cin * PSFM_DEC_TILE; idx += PSFM_DEC_THREADS) {
             const int c = idx >> 6, p = idx & 63;
             float v = 0.0f;
             if (p < np) {
-                v = S.src[c * k + p0 + p];
-                if (S.stat) v = psfm_dec_norm_relu(v, fm[c], fs[c], ft[c]);
+                v = src[c * k + p0 + p];
+                if (stat) v = psfm_dec_norm_relu(v, fm[c], fs[c], ft[c]);
             }
             ldsX[p * PSFM_DEC_LDX + c] = v;
         }
@@ -95,11 +118,13 @@ __global__ __launch_bounds__(PSFM_DEC_THREADS) void psfm_dec_layer_kernel(const 
         if (tid < PSFM_DEC_TILE) psfm_dec_softmax_clusters(ldsX + tid * PSFM_DEC_LDX);
 #pragma unroll
         for (int r = 0; r < 16; r++) acc[0][r] = acc[1][r] = 0.0f;
-        pd_gemm<2, false>(acc, Y.x2, PSFM_DEC_CL, PSFM_DEC_CL, PSFM_DEC_C, ldsW, ldsX, PSFM_DEC_LDX, tid);
+        pd_gemm<2, false>(acc, at(Y.x2), PSFM_DEC_CL, PSFM_DEC_CL, PSFM_DEC_C, ldsW, ldsX, PSFM_DEC_LDX, tid);
         __syncthreads();
     }
 
     // the block's output tile: to memory, and as the image [point][channel] for what is reduced over it
+    const float* residual = at(Y.residual);
+    float* out = at(Y.out);
 #pragma unroll
     for (int t = 0; t < 2; t++)
 #pragma unroll
@@ -108,8 +133,8 @@ __global__ __launch_bounds__(PSFM_DEC_THREADS) void psfm_dec_layer_kernel(const 
             float v = acc[t][r];
             if (Y.mode != PSFM_DEC_UNPOOL && Y.bias2 && row < Y.cout) v += Y.bias2[row];
             const bool live = pc < np && (Y.mode == PSFM_DEC_UNPOOL || row < Y.cout);
-            if (live && Y.residual) v += Y.residual[row * k + p0 + pc];
-            if (live && Y.mode != PSFM_DEC_FINAL) Y.out[row * k + p0 + pc] = v;
+            if (live && residual) v += residual[row * k + p0 + pc];
+            if (live && Y.mode != PSFM_DEC_FINAL) out[row * k + p0 + pc] = v;
             ldsX[pc * PSFM_DEC_LDX + row] = v;
         }
     __syncthreads();
@@ -119,9 +144,9 @@ __global__ __launch_bounds__(PSFM_DEC_THREADS) void psfm_dec_layer_kernel(const 
             float logit, prob;
             uint8_t pred;
             psfm_dec_verdict(ldsX + tid * PSFM_DEC_LDX, Y.wout, logit, prob, pred);
-            if (Y.logits) Y.logits[p0 + tid] = logit;
-            if (Y.prob) Y.prob[p0 + tid] = prob;
-            if (Y.pred) Y.pred[p0 + tid] = pred;
+            if (at.logits(Y)) at.logits(Y)[p0 + tid] = logit;
+            if (at.prob(Y)) at.prob(Y)[p0 + tid] = prob;
+            if (at.pred(Y)) at.pred(Y)[p0 + tid] = pred;
         }
         return;
     }
@@ -136,7 +161,7 @@ __global__ __launch_bounds__(PSFM_DEC_THREADS) void psfm_dec_layer_kernel(const 
         const double o = __shfl_xor(s, 1);
         s = half ? o + s : s + o;
         if (!half && c < PSFM_DEC_CL) {
-            double* dst = Y.part + ((size_t)blockIdx.x * PSFM_DEC_CL + c) * 2;
+            double* dst = at(Y.part) + ((size_t)blk * PSFM_DEC_CL + c) * 2;
             dst[0] = (double)m;
             dst[1] = s;
         }
@@ -151,7 +176,7 @@ __global__ __launch_bounds__(PSFM_DEC_THREADS) void psfm_dec_layer_kernel(const 
         s = half ? so + s : s + so;
         q = half ? qo + q : q + qo;
         if (!half) {
-            double* dst = Y.part + ((size_t)blockIdx.x * PSFM_DEC_C + c) * 2;
+            double* dst = at(Y.part) + ((size_t)blk * PSFM_DEC_C + c) * 2;
             dst[0] = s;
             dst[1] = q;
         }
@@ -159,7 +184,7 @@ __global__ __launch_bounds__(PSFM_DEC_THREADS) void psfm_dec_layer_kernel(const 
 }
 
 // The blocks' partial sums of channel blockIdx.x in the fixed order of psfm_decoder.h -> fin[c] = mean, fin[128 + c] = inv.
-__global__ __launch_bounds__(PSFM_DEC_THREADS) void psfm_dec_stats_kernel(const double* __restrict__ part, int nb, int k, double* __restrict__ fin)
+__device__ __forceinline__ void pd_stats(const double* __restrict__ part, int nb, int k, double* __restrict__ fin)
 {
     __shared__ double a[PSFM_DEC_THREADS], b[PSFM_DEC_THREADS];
     const int tid = (int)threadIdx.x, c = (int)blockIdx.x;
@@ -179,7 +204,7 @@ __global__ __launch_bounds__(PSFM_DEC_THREADS) void psfm_dec_stats_kernel(const 
 }
 
 // down1: the blocks' (max, sum of exponentials) of cluster blockIdx.x -> sm_fin[2 j] = M, [2 j + 1] = 1 / sum.
-__global__ __launch_bounds__(PSFM_DEC_THREADS) void psfm_dec_softmax_kernel(const double* __restrict__ part, int nb, float* __restrict__ sm_fin)
+__device__ __forceinline__ void pd_softmax(const double* __restrict__ part, int nb, float* __restrict__ sm_fin)
 {
     __shared__ double a[PSFM_DEC_THREADS];
     const int tid = (int)threadIdx.x, j = (int)blockIdx.x;
@@ -209,13 +234,14 @@ __global__ __launch_bounds__(PSFM_DEC_THREADS) void psfm_dec_softmax_kernel(cons
     }
 }
 
-// down1: x1_1 S^T over this block's PSFM_DEC_SLICE points as a partial [128][100]; wave w holds channels 32 w .. against all clusters.
-__global__ __launch_bounds__(PSFM_DEC_THREADS) void psfm_dec_pool_kernel(const float* __restrict__ x1, const float* __restrict__ emb,
-                                                                       const float* __restrict__ sm_fin, int k, float* __restrict__ part)
+// down1: x1_1 S^T over the PSFM_DEC_SLICE points of slice `blk` as a partial [128][100]; wave w holds channels 32 w .. against all
+// clusters.
+__device__ __forceinline__ void pd_pool(const float* __restrict__ x1, const float* __restrict__ emb, const float* __restrict__ sm_fin, int k,
+                                        float* __restrict__ part, int blk)
 {
     __shared__ float ldsA[PSFM_DEC_C * PSFM_DEC_LDW], ldsB[PSFM_DEC_C * PSFM_DEC_LDW];
     const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int base = (int)blockIdx.x * PSFM_DEC_SLICE;
+    const int base = blk * PSFM_DEC_SLICE;
     f32x16 acc[4];
 #pragma unroll
     for (int t = 0; t < 4; t++)
@@ -232,7 +258,7 @@ __global__ __launch_bounds__(PSFM_DEC_THREADS) void psfm_dec_pool_kernel(const f
         __syncthreads();
         pd_mma<4>(acc, ldsA + wave * 32 * PSFM_DEC_LDW, PSFM_DEC_LDW, ldsB, PSFM_DEC_LDW, PSFM_DEC_KC, lane);
     }
-    float* dst = part + (size_t)blockIdx.x * PSFM_DEC_C * PSFM_DEC_CL;
+    float* dst = part + (size_t)blk * PSFM_DEC_C * PSFM_DEC_CL;
 #pragma unroll
     for (int t = 0; t < 4; t++)
 #pragma unroll
@@ -282,8 +308,7 @@ __device__ __forceinline__ void pd_l2_norm(const f32x16 (&v)[4], const float* bn
         }
 }
 
-__global__ __launch_bounds__(PSFM_DEC_THREADS) void psfm_dec_l2_kernel(const float* __restrict__ part, int nb2, const float* __restrict__ w,
-                                                                     float* __restrict__ x2)
+__device__ __forceinline__ void pd_l2(const float* __restrict__ part, int nb2, const float* __restrict__ w, float* __restrict__ x2)
 {
     extern __shared__ float smem[];
     float* img = smem;
@@ -351,6 +376,73 @@ __global__ __launch_bounds__(PSFM_DEC_THREADS) void psfm_dec_l2_kernel(const flo
         }
 }
 
+// ---- the kernels: one window (psfm_traj_decode) ------------------------------------------------------------------------------
+__global__ __launch_bounds__(PSFM_DEC_THREADS) void psfm_dec_layer_kernel(const PsfmDecLayer Y, int k) { pd_layer(Y, PdOne(), k, (int)blockIdx.x); }
+
+__global__ __launch_bounds__(PSFM_DEC_THREADS) void psfm_dec_stats_kernel(const double* __restrict__ part, int nb, int k, double* __restrict__ fin)
+{
+    pd_stats(part, nb, k, fin);
+}
+
+__global__ __launch_bounds__(PSFM_DEC_THREADS) void psfm_dec_softmax_kernel(const double* __restrict__ part, int nb, float* __restrict__ sm_fin)
+{
+    pd_softmax(part, nb, sm_fin);
+}
+
+__global__ __launch_bounds__(PSFM_DEC_THREADS) void psfm_dec_pool_kernel(const float* __restrict__ x1, const float* __restrict__ emb,
+                                                                       const float* __restrict__ sm_fin, int k, float* __restrict__ part)
+{
+    pd_pool(x1, emb, sm_fin, k, part, (int)blockIdx.x);
+}
+
+__global__ __launch_bounds__(PSFM_DEC_THREADS) void psfm_dec_l2_kernel(const float* __restrict__ part, int nb2, const float* __restrict__ w,
+                                                                     float* __restrict__ x2)
+{
+    pd_l2(part, nb2, w, x2);
+}
+
+// ---- the kernels: a batch of windows (psfm_traj_decode_batch, psfm_decoder_batch.h) -------------------------------------------
+// The same bodies; a block first finds its window in the table B and then works on that window's k, sections and partial-sum rows.
+// Y and fin hold section names.
+__global__ __launch_bounds__(PSFM_DEC_THREADS) void psfm_dec_layer_batch_kernel(const PsfmDecLayer Y, const PsfmDecBatch B)
+{
+    const int b = psfm_dec_batch_find(B.tile0, (int)blockIdx.x);
+    const PdWin at = {psfm_dec_batch_window(B, b), B.logits[b], B.prob[b], B.pred[b]};
+    pd_layer(Y, at, at.W.k, (int)blockIdx.x - B.tile0[b]);
+}
+
+__global__ __launch_bounds__(PSFM_DEC_THREADS) void psfm_dec_stats_batch_kernel(const PsfmDecBatch B, double* fin)
+{
+    const int b = (int)blockIdx.y;
+    if (B.k[b] == 0) return;
+    const PsfmDecWin W = psfm_dec_batch_window(B, b);
+    pd_stats((const double*)(W.base + W.L.stat_part), W.L.nb, W.k, psfm_dec_resolve(fin, W));
+}
+
+__global__ __launch_bounds__(PSFM_DEC_THREADS) void psfm_dec_softmax_batch_kernel(const PsfmDecBatch B)
+{
+    const int b = (int)blockIdx.y;
+    if (B.k[b] == 0) return;
+    const PsfmDecWin W = psfm_dec_batch_window(B, b);
+    pd_softmax((const double*)(W.base + W.L.sm_part), W.L.nb, (float*)(W.base + W.L.sm_fin));
+}
+
+__global__ __launch_bounds__(PSFM_DEC_THREADS) void psfm_dec_pool_batch_kernel(const PsfmDecBatch B)
+{
+    const int b = psfm_dec_batch_find(B.slice0, (int)blockIdx.x);
+    const PsfmDecWin W = psfm_dec_batch_window(B, b);
+    pd_pool((const float*)(W.base + W.L.x1), (const float*)(W.base + W.L.emb), (const float*)(W.base + W.L.sm_fin), W.k,
+            (float*)(W.base + W.L.pool_part), (int)blockIdx.x - B.slice0[b]);
+}
+
+__global__ __launch_bounds__(PSFM_DEC_THREADS) void psfm_dec_l2_batch_kernel(const PsfmDecBatch B, const float* __restrict__ w)
+{
+    const int b = (int)blockIdx.x;
+    if (B.k[b] == 0) return;
+    const PsfmDecWin W = psfm_dec_batch_window(B, b);
+    pd_l2((const float*)(W.base + W.L.pool_part), W.L.nb2, w, (float*)(W.base + W.L.x2));
+}
+
 extern "C" int psfm_traj_decode_weight_count(void) { return PSFM_DEC_WEIGHTS; }
 
 extern "C" size_t psfm_traj_decode_workspace_bytes(int64_t k) { return k > 0 && k <= PSFM_DEC_MAX_K ? psfm_dec_workspace(k).total : 0; }
@@ -399,6 +491,84 @@ extern "C" psfm_status psfm_traj_decode(psfm_ctx* c, const float* encoding, cons
         case PSFM_DEC_STEP_L2:
             hipLaunchKernelGGL(psfm_dec_l2_kernel, dim3(1), dim3(PSFM_DEC_THREADS), PD_L2_LDS, s, (const float*)P.pool_part, P.nb2,
                                weights + PSFM_DEC_W_L2, P.x2);
+            break;
+        }
+    }
+    PSFM_HIP(hipGetLastError());
+    return PSFM_OK;
+}
+
+extern "C" size_t psfm_traj_decode_batch_workspace_bytes(const int64_t* k, int n_win)
+{
+    static thread_local PsfmDecBatch B;
+    size_t total;
+    int bad;
+    if (n_win < 0 || n_win > PSFM_DEC_BATCH_MAX || (n_win > 0 && !k)) return 0;
+    return psfm_dec_batch_layout(B, k, n_win, total, bad) == PSFM_DEC_BATCH_OK ? total : 0;
+}
+
+extern "C" psfm_status psfm_traj_decode_batch(psfm_ctx* c, int n_win, const float* const* encoding, const int64_t* k, const float* weights,
+                                              void* workspace, size_t workspace_bytes, float* const* logits, float* const* prob,
+                                              uint8_t* const* pred, void* stream)
+{
+    if (!c) { psfm_set_error("ctx is NULL"); return PSFM_ERR_ARG; }
+    if (n_win < 0 || n_win > PSFM_DEC_BATCH_MAX) {
+        psfm_set_error("psfm_traj_decode_batch: bad argument (n_win=%d, supported is 0 <= n_win <= %d)", n_win, PSFM_DEC_BATCH_MAX);
+        return PSFM_ERR_ARG;
+    }
+    if (n_win == 0) return PSFM_OK;
+    if (!k) { psfm_set_error("psfm_traj_decode_batch: k is NULL"); return PSFM_ERR_ARG; }
+    static thread_local PsfmDecBatch B;
+    size_t need;
+    int bad;
+    if (psfm_dec_batch_layout(B, k, n_win, need, bad) != PSFM_DEC_BATCH_OK) {
+        if (k[bad] == 1)
+            psfm_set_error("psfm_traj_decode_batch: window %d: k=1: InstanceNorm2d needs more than one point (the reference raises here)", bad);
+        else
+            psfm_set_error("psfm_traj_decode_batch: window %d: bad argument (k=%lld, supported is 0 or 2 <= k <= %lld)", bad, (long long)k[bad],
+                           (long long)PSFM_DEC_MAX_K);
+        return PSFM_ERR_ARG;
+    }
+    if (B.tiles == 0) return PSFM_OK;                       // every window is empty
+    if (!encoding || !weights || !workspace) { psfm_set_error("psfm_traj_decode_batch: NULL argument"); return PSFM_ERR_ARG; }
+    for (int b = 0; b < n_win; b++)
+        if (k[b] > 0 && !encoding[b]) { psfm_set_error("psfm_traj_decode_batch: window %d: encoding is NULL (k=%lld)", b, (long long)k[b]); return PSFM_ERR_ARG; }
+    if (workspace_bytes < need) {
+        psfm_set_error("psfm_traj_decode_batch: workspace_bytes=%zu, these %d windows need %zu (psfm_traj_decode_batch_workspace_bytes)",
+                       workspace_bytes, n_win, need);
+        return PSFM_ERR_ARG;
+    }
+    for (int b = 0; b < n_win; b++) {
+        B.enc[b] = encoding[b];
+        B.logits[b] = logits ? logits[b] : 0;
+        B.prob[b] = prob ? prob[b] : 0;
+        B.pred[b] = pred ? pred[b] : 0;
+    }
+    B.ws = (char*)workspace;
+    PSFM_HIP(hipSetDevice(c->device));
+    PSFM_HIP(hipFuncSetAttribute((const void*)psfm_dec_l2_batch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PD_L2_LDS));
+    PsfmGate gate(c->device, 0);
+    static thread_local PsfmDecPlan P;
+    psfm_dec_plan_names(P, weights);
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 threads(PSFM_DEC_THREADS);
+    for (int i = 0; i < P.nsteps; i++) {
+        const PsfmDecStep& S = P.step[i];
+        switch (S.kind) {
+        case PSFM_DEC_STEP_LAYER:
+            hipLaunchKernelGGL(psfm_dec_layer_batch_kernel, dim3((unsigned)B.tiles), threads, 0, s, S.layer, B);
+            break;
+        case PSFM_DEC_STEP_STATS:
+            hipLaunchKernelGGL(psfm_dec_stats_batch_kernel, dim3(PSFM_DEC_C, (unsigned)n_win), threads, 0, s, B, S.fin);
+            break;
+        case PSFM_DEC_STEP_SOFTMAX:
+            hipLaunchKernelGGL(psfm_dec_softmax_batch_kernel, dim3(PSFM_DEC_CL, (unsigned)n_win), threads, 0, s, B);
+            break;
+        case PSFM_DEC_STEP_POOL:
+            hipLaunchKernelGGL(psfm_dec_pool_batch_kernel, dim3((unsigned)B.slices), threads, 0, s, B);
+            break;
+        case PSFM_DEC_STEP_L2:
+            hipLaunchKernelGGL(psfm_dec_l2_batch_kernel, dim3((unsigned)n_win), threads, PD_L2_LDS, s, B, weights + PSFM_DEC_W_L2);
             break;
         }
     }

@@ -28,6 +28,7 @@ EXPORTS = [
     "psfm_labels_begin", "psfm_labels_merge_window", "psfm_labels_finish", "psfm_labels_device", "psfm_labels_copy", "psfm_labels_to_matches",
     "psfm_traj_augment", "psfm_traj_encode_weight_count", "psfm_traj_encode",
     "psfm_traj_decode_weight_count", "psfm_traj_decode_workspace_bytes", "psfm_traj_decode",
+    "psfm_traj_decode_batch_workspace_bytes", "psfm_traj_decode_batch",
     "psfm_traj_eval_counts", "psfm_traj_vote_labels",
     "psfm_labels_set", "psfm_matches_to_database", "psfm_database_copy", "psfm_database_chunk_rows",
     "psfm_database_compact_again",
@@ -125,6 +126,9 @@ def lib():
     L.psfm_traj_decode_weight_count.argtypes = []
     L.psfm_traj_decode_workspace_bytes.argtypes = [i64]
     L.psfm_traj_decode.argtypes = [vp, vp, vp, i64, vp, ctypes.c_size_t, vp, vp, vp, vp]
+    L.psfm_traj_decode_batch_workspace_bytes.argtypes = [ctypes.POINTER(i64), i32]
+    L.psfm_traj_decode_batch.argtypes = [vp, i32, ctypes.POINTER(vp), ctypes.POINTER(i64), vp, vp, ctypes.c_size_t, ctypes.POINTER(vp),
+                                         ctypes.POINTER(vp), ctypes.POINTER(vp), vp]
     L.psfm_traj_eval_counts.argtypes = [vp, vp, vp, vp, i64, vp, vp, i32, i32, i32, vp, vp]
     L.psfm_traj_vote_labels.argtypes = [vp, vp, vp, vp, i64, i32, i32, i32, vp, vp]
     L.psfm_traj_to_matches.argtypes = [vp, i32, i32, vp, ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(i64), vp]
@@ -180,6 +184,7 @@ def lib():
         if name != "psfm_last_error":
             getattr(L, name).restype = i32
     L.psfm_traj_decode_workspace_bytes.restype = ctypes.c_size_t
+    L.psfm_traj_decode_batch_workspace_bytes.restype = ctypes.c_size_t
     _lib = L
     return L
 

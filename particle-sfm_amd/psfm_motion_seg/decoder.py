@@ -157,3 +157,62 @@ def device_predictor(enc_weights, dec_weights, depth_for_window, input_size, kin
         enc = encode_traj_device(feat, mask, enc_weights, ctx=ctx)
         return decode_traj_device(enc, dec_weights, ctx=ctx)[2]
     return predict
+
+
+BATCH_MAX = 64                 # PSFM_DEC_BATCH_MAX of csrc/psfm_decoder_batch.h: windows per psfm_traj_decode_batch call
+
+
+def decode_windows_device(encodings, weights, ctx=None, workspace=None):
+    """decode_traj_device for a list of windows through psfm_traj_decode_batch: ONE sequence of launches per call of at most BATCH_MAX
+    windows (longer lists are split) instead of one per window.  encodings: a list of (1,16,K_b) or (16,K_b) fp32 tensors, the K_b
+    may differ and may be 0; workspace: a device tensor of at least psfm_traj_decode_batch_workspace_bytes bytes for every call
+    (default: the one cached per device, grown on demand).  Returns a list of (logits (1,1,K_b), prob (1,1,K_b), pred (K_b,) bool),
+    each bit-identical to decode_traj_device on that window alone.  Asynchronous on the current stream."""
+    import ctypes
+    import torch
+    from point_trajectory import _hip
+    ctx = ctx or _hip.context()                       # (no device: RuntimeError)
+    dev = torch.device("cuda", ctx.device)
+    weights = torch.as_tensor(weights)
+    if weights.numel() != WEIGHT_COUNT:
+        raise ValueError("decode_windows_device: weights has %d elements, pack_decoder_weights gives %d" % (weights.numel(), WEIGHT_COUNT))
+    encs = []
+    for b, e in enumerate(encodings):
+        e = torch.as_tensor(e)
+        if e.dim() == 3 and e.shape[0] == 1:
+            e = e[0]
+        if e.dim() != 2 or e.shape[0] != D_IN:
+            raise ValueError("decode_windows_device: window %d: encoding must be (1,16,K) or (16,K), got %s" % (b, tuple(e.shape)))
+        if int(e.shape[1]) == 1:
+            raise ValueError("decode_windows_device: window %d: K = 1: the decoder's InstanceNorm2d needs more than one trajectory "
+                             "(the reference raises)" % b)
+        encs.append(e.to(dev).float().contiguous())
+    wts = weights.to(dev).float().contiguous()
+    L, vp = _hip.lib(), ctypes.c_void_p
+    out = []
+    for lo in range(0, len(encs), BATCH_MAX):
+        part = encs[lo:lo + BATCH_MAX]
+        n = len(part)
+        ks = [int(e.shape[1]) for e in part]
+        k = (ctypes.c_int64 * n)(*ks)
+        need = int(L.psfm_traj_decode_batch_workspace_bytes(k, n))
+        ws = workspace
+        if ws is None:
+            ws = _workspace(dev, need)
+        elif not ws.is_cuda or not ws.is_contiguous() or ws.numel() * ws.element_size() < need:
+            raise ValueError("decode_windows_device: workspace must be a contiguous device tensor of at least %d bytes" % need)
+        # one allocation per output kind; the windows' tensors are views of it
+        total = sum(ks)
+        logits = torch.empty((total,), dtype=torch.float32, device=dev)
+        prob = torch.empty((total,), dtype=torch.float32, device=dev)
+        pred = torch.empty((total,), dtype=torch.uint8, device=dev)
+        views, at = [], 0
+        for kb in ks:
+            views.append((logits[at:at + kb], prob[at:at + kb], pred[at:at + kb]))
+            at += kb
+        col = lambda ts: (vp * n)(*[t.data_ptr() if t.numel() else None for t in ts])
+        _hip.check(L.psfm_traj_decode_batch(ctx.handle, n, col(part), k, _hip.ptr(wts), _hip.ptr(ws), ws.numel() * ws.element_size(),
+                                            col([v[0] for v in views]), col([v[1] for v in views]), col([v[2] for v in views]),
+                                            _hip.current_stream_ptr(ctx.device)))
+        out += [(lo_.view(1, 1, -1), pr.view(1, 1, -1), pd.view(torch.bool)) for lo_, pr, pd in views]
+    return out

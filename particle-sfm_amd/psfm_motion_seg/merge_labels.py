@@ -157,3 +157,101 @@ def label_trajectories(length, window, raw_hw, input_size, traj_max_num, predict
         merger.window_ids.append(ids)
     merger.finish()
     return merger
+
+
+# Rows (trajectories over all windows) that one decode group may hold: psfm_traj_decode_batch needs its windows' workspaces at the
+# same time, 2.6 KB per row, so 2^18 rows bound the workspace at about 0.7 GB -- two and a half windows at the shipped cap of 100 000
+# trajectories, tens of windows of a DAVIS-sized sequence.  A window above the cap forms a group of its own.
+DEFAULT_MAX_ROWS = 1 << 18
+
+
+def _sample_and_encode(ctx, length, window, raw_hw, input_size, traj_max_num, enc_weights, depth_of, seed, traj_min_len, kinv):
+    """Phase 1 for one context: the saved set, the merger, and per window (frame0, n_frames, ids, encoding (1,16,K), mask_absent)."""
+    from point_trajectory import _hip
+    from .augment import augment_traj_device
+    from .encoder import encode_traj_device
+    from .load_cut_seq import sample_window_device, window_ranges
+    k, n = ctypes.c_int64(0), ctypes.c_int64(0)
+    _hip.check(_hip.lib().psfm_result_filter(ctx.handle, int(traj_min_len), ctypes.byref(k), ctypes.byref(n), _hip.current_stream_ptr(ctx.device)))
+    merger = LabelMerger(ctx)
+    windows = []
+    for w, (f0, nf) in enumerate(window_ranges(length, window)):
+        ids, raw, nor, mask = sample_window_device(ctx, f0, nf, raw_hw, input_size, traj_max_num, 3, traj_min_len, seed + w)
+        feat = augment_traj_device(nor, mask, depth_of(np.arange(f0, f0 + nf)), input_size, kinv=kinv, ctx=ctx)
+        windows.append((f0, nf, ids, encode_traj_device(feat, mask, enc_weights, ctx=ctx), mask))
+    return merger, windows
+
+
+def decode_groups(rows, max_rows=None):
+    """Consecutive windows with `rows` trajectories each -> [(first, last + 1), ...]: a group closes before the window that would take
+    it above max_rows (default DEFAULT_MAX_ROWS); a window larger than that stands alone."""
+    cap = DEFAULT_MAX_ROWS if max_rows is None else int(max_rows)
+    groups, lo, total = [], 0, 0
+    for i, r in enumerate(rows):
+        if i > lo and total + int(r) > cap:
+            groups.append((lo, i))
+            lo, total = i, 0
+        total += int(r)
+    if len(rows) > lo:
+        groups.append((lo, len(rows)))
+    return groups
+
+
+def _decode_and_merge(mergers, windows_per_ctx, dec_weights, ctx, max_rows):
+    """Phases 2 and 3: every window of every context through decode_windows_device in groups of consecutive windows, then add_window
+    per context in window order and finish."""
+    from .decoder import decode_windows_device
+    flat = [w for windows in windows_per_ctx for w in windows]
+    preds = []
+    for lo, hi in decode_groups([int(w[2].numel()) for w in flat], max_rows):
+        preds += [p[2] for p in decode_windows_device([w[3] for w in flat[lo:hi]], dec_weights, ctx=ctx)]
+    at = 0
+    for merger, windows in zip(mergers, windows_per_ctx):
+        merger.window_ids = []
+        for (f0, nf, ids, _, _), pred in zip(windows, preds[at:at + len(windows)]):
+            merger.add_window(f0, nf, ids, pred)
+            merger.window_ids.append(ids)
+        at += len(windows)
+        merger.finish()
+
+
+def label_trajectories_batched(length, window, raw_hw, input_size, traj_max_num, enc_weights, dec_weights, depth_for_window, seed=0,
+                               traj_min_len=3, kinv=None, ctx=None, max_rows=None):
+    """label_trajectories(..., predict=decoder.device_predictor(enc_weights, dec_weights, depth_for_window, input_size, kinv, ctx))
+    with the decoder run once per GROUP of windows instead of once per window: the same saved set, the same windows
+    (load_cut_seq.window_ranges), the same seeds (seed + w), the same merger, the same bytes out of finish().
+      1. per window: sample_window_device, augment_traj_device (depth_for_window(time_idx) as device_predictor calls it),
+         encode_traj_device; the ids, the encoding and the mask are kept;
+      2. decoder.decode_windows_device over groups of consecutive windows (decode_groups: at most max_rows trajectories per group,
+         default DEFAULT_MAX_ROWS, so that the group's workspace, 2.6 KB per row, stays bounded).  A window's result is that of
+         psfm_traj_decode on the window alone, so the grouping changes no bit;
+      3. LabelMerger.add_window in window order, then finish().
+    Returns the merger, finished, with `window_ids`."""
+    from point_trajectory import _hip
+    ctx = ctx or _hip.context()
+    merger, windows = _sample_and_encode(ctx, length, window, raw_hw, input_size, traj_max_num, enc_weights, depth_for_window, seed,
+                                         traj_min_len, kinv)
+    _decode_and_merge([merger], [windows], dec_weights, ctx, max_rows)
+    return merger
+
+
+def label_sequences_batched(ctxs, lengths, window, raw_hw, input_size, traj_max_num, enc_weights, dec_weights, depth_for_window, seed=0,
+                            traj_min_len=3, kinv=None, max_rows=None):
+    """label_trajectories_batched for several contexts on one device -- what trajectory.run_connect_batch returns -- with the windows
+    of ALL sequences going through the same decode groups: sequence after sequence, window after window.  lengths[i]: frames of
+    sequence i; depth_for_window(seq_index, time_idx).  Sampling, augment and encode (phase 1) and the merge (phase 3) stay per context;
+    every context's labelled set equals what label_trajectories_batched gives for it alone.  Returns the finished mergers."""
+    ctxs = list(ctxs)
+    if len(ctxs) != len(lengths):
+        raise ValueError("label_sequences_batched: %d contexts, %d lengths" % (len(ctxs), len(lengths)))
+    if any(c.device != ctxs[0].device for c in ctxs):
+        raise ValueError("label_sequences_batched: the contexts must be on one device")
+    mergers, per_ctx = [], []
+    for i, (ctx, length) in enumerate(zip(ctxs, lengths)):
+        merger, windows = _sample_and_encode(ctx, int(length), window, raw_hw, input_size, traj_max_num, enc_weights,
+                                             lambda t, i=i: depth_for_window(i, t), seed, traj_min_len, kinv)
+        mergers.append(merger)
+        per_ctx.append(windows)
+    if ctxs:
+        _decode_and_merge(mergers, per_ctx, dec_weights, ctxs[0], max_rows)
+    return mergers
