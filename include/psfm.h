@@ -492,6 +492,56 @@ psfm_status psfm_traj_decode_batch(psfm_ctx* ctx, int n_win, const float* const*
                                    void* workspace, size_t workspace_bytes, float* const* logits, float* const* prob,
                                    uint8_t* const* pred, void* stream);
 
+/* The front end of the motion classifier for n_win windows in one pass each: what psfm_traj_decode_batch is to psfm_traj_decode,
+ * the three calls below are to psfm_window_sample, psfm_traj_augment and psfm_traj_encode.  No new rule: every window's tensors are
+ * BIT-IDENTICAL to the single call on that window alone.  Conventions of psfm_traj_decode_batch: HOST arrays of per-window values
+ * and DEVICE pointers, read before the call returns; the per-window table travels by value in the kernel arguments; 0 <= n_win <= 64
+ * (callers split longer lists); PSFM_ERR_ARG with nothing launched on a bad argument, the message names the first offending window.
+ * No floating-point atomics; identical calls give identical bytes.
+ *
+ * psfm_window_sample_batch   psfm_window_sample(frame0[b], n_frames, ..., seed[b]) for every window b of ONE context, on the result
+ *   of its last psfm_track / psfm_connect.  Windows share n_frames; they may overlap; one outside the sequence has k = 0; k = 1 is
+ *   legal.  Window b occupies rows [sum of k[a] for a < b, + k[b]) of each output, so its block is a contiguous (k[b], n_frames, .)
+ *   tensor: the same ids in the same order (ascending at or below max_num_tracks; above it the max_num_tracks smallest splitmix64
+ *   keys of (seed[b], id) in key order, equal keys in ascending id order), the same xy_raw, xy_norm and mask_absent, byte for byte.
+ *   `capacity` = rows the outputs can hold over all windows; k_host[b] = the window's rows.
+ *     PLAN   all four outputs NULL: the selection is made for all windows in one pass over the trajectories -- per-(window, block)
+ *            counts by ballots, one fixed-order integer scan, one compaction; per window above the cap one hash and one stable 64-bit
+ *            sort -- and KEPT in workspace the context owns.  Synchronises `stream` ONCE, for all windows together.
+ *     FILL   any output given, and a plan is kept for the same n_win, frame0[], n_frames, traj_min_len, min_length, max_num_tracks
+ *            and seed[] on the same result: ONE gather launch over the rows of all windows.  ASYNCHRONOUS on `stream` (the stream of
+ *            the plan call, or one ordered behind it): no synchronisation, no allocation.  capacity below the sum of k:
+ *            PSFM_ERR_CAPACITY, nothing written.
+ *            Without a matching plan the call makes the plan itself (one synchronisation), then gathers.  A stale plan is never
+ *            used: psfm_track, psfm_connect, psfm_connect_batch, psfm_track_queries, psfm_track_queries_optimize and
+ *            psfm_result_filter on the context void it, as does any differing argument.
+ *   PSFM_ERR_ARG: n_win outside [0, 64], n_frames < 1, max_num_tracks < 0, capacity < 0, a NULL host array with n_win > 0, sizes < 1
+ *   with xy_norm given, a window whose frame0 + n_frames leaves the 32-bit range.
+ *
+ * psfm_traj_augment_batch    psfm_traj_augment for n_win windows of n_frames frames and one (h, w, kinv) in ONE launch.  xy_norm[b]
+ *   (k[b],n_frames,2) f64, mask_absent[b] (k[b],n_frames) f64, depth[b] (n_frames,h,w) f32, out[b] [10][k[b]][n_frames] f32: views
+ *   of psfm_window_sample_batch's outputs, or any other buffers.  Blocks of 256 elements are numbered inside a window.  k[b] == 0
+ *   skips the window (its pointers may be NULL, nothing of it is touched).  The single call's limits hold per window (h*w and
+ *   10*k[b]*n_frames at most 2^31 - 1).  ASYNCHRONOUS, no allocation.  n_win == 0 or every k[b] == 0: PSFM_OK, nothing launched.
+ *   PSFM_ERR_ARG: n_win outside [0, 64], n_frames, h or w < 1, a k[b] < 0 or above the limit, a NULL entry with k[b] > 0.
+ *
+ * psfm_traj_encode_batch     psfm_traj_encode for n_win windows of n_frames frames with one set of weights in ONE launch.
+ *   features[b] [10][k[b]][n_frames] f32, mask_absent[b] (k[b],n_frames) f64, out[b] [16][k[b]] f32 (what psfm_traj_decode_batch
+ *   takes as encoding[b]).  Blocks are numbered inside a window, so the packing of trajectories into waves is the single call's; the
+ *   kernel has the vector registers and the LDS of the single one, the window costs scalar registers only.  1 <= n_frames <= 64.
+ *   ASYNCHRONOUS, no allocation.  k[b] == 0 skips the window; n_win == 0 or every k[b] == 0: PSFM_OK, nothing launched.
+ *   PSFM_ERR_ARG: n_win outside [0, 64], n_frames outside [1, 64], a k[b] < 0 or above the single call's limit, a NULL entry with
+ *   k[b] > 0, NULL weights. */
+psfm_status psfm_window_sample_batch(psfm_ctx* ctx, int n_win, const int* frame0, int n_frames, int traj_min_len, int min_length,
+                                     int64_t max_num_tracks, const uint64_t* seed, int raw_h, int raw_w, int in_h, int in_w,
+                                     int64_t capacity, int32_t* ids_out, double* xy_raw, double* xy_norm, double* mask_absent,
+                                     int64_t* k_host, void* stream);
+psfm_status psfm_traj_augment_batch(psfm_ctx* ctx, int n_win, const double* const* xy_norm, const double* const* mask_absent,
+                                    const float* const* depth, const int64_t* k, int n_frames, int h, int w, const float* kinv_host,
+                                    float* const* out, void* stream);
+psfm_status psfm_traj_encode_batch(psfm_ctx* ctx, int n_win, const float* const* features, const double* const* mask_absent,
+                                   const float* weights, const int64_t* k, int n_frames, float* const* out, void* stream);
+
 /* sfm/matches_from_flow.py:51-118 (traj_to_matches) from the saved set that psfm_result_filter left in HBM -- the
  * reference's per-trajectory Python loops as index arithmetic on the device (no track.npy round trip):
  *   keypoints  image i lists the kept points observed in frame i in trajectory (id) order (:67-81); labels_dev: optional

@@ -245,18 +245,23 @@ __device__ __forceinline__ void psfm_enc_phase(int p, PsfmEncTok& s, const float
 #pragma unroll
             for (int i = 0; i < 16; i++) s.cur[i] = s.x[i];
         }
-        if (p == PSFM_ENC_PHASES - 1) {
-            psfm_enc_ln(s.cur, w + PSFM_ENC_W_DEC_NORM);
-#pragma unroll
-            for (int i = 0; i < 16; i++) s.pub[i] = s.cur[i];
-            return;
-        }
+        if (p == PSFM_ENC_PHASES - 1) psfm_enc_ln(s.cur, w + PSFM_ENC_W_DEC_NORM);
     }
+    // the row to exchange: the K | V of the attention that starts here, or (last phase) the token's output in [0,16).  Written in ONE
+    // place: two places leave the compiler two floats of pub in scratch (it merges their last stores through a selected address)
+    const bool last = p == PSFM_ENC_PHASES - 1;
     const bool from_mem = p == 3 || p == 5;
-    float kv[PSFM_ENC_D];
+    float row[2 * PSFM_ENC_D];
 #pragma unroll
-    for (int i = 0; i < 16; i++) kv[i] = from_mem ? s.mem[i] : s.cur[i];
-    psfm_enc_qkv(w + n.start, s.cur, kv, s.q, s.pub);
+    for (int i = 0; i < 2 * PSFM_ENC_D; i++) row[i] = i < PSFM_ENC_D ? s.cur[i] : s.pub[i];
+    if (!last) {
+        float kv[PSFM_ENC_D];
+#pragma unroll
+        for (int i = 0; i < 16; i++) kv[i] = from_mem ? s.mem[i] : s.cur[i];
+        psfm_enc_qkv(w + n.start, s.cur, kv, s.q, row);
+    }
+#pragma unroll
+    for (int i = 0; i < 2 * PSFM_ENC_D; i++) s.pub[i] = row[i];
 }
 
 // feature c of a trajectory from the rows exchanged behind the last phase: the max over ALL L tokens

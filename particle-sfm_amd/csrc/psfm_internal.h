@@ -209,6 +209,20 @@ struct psfm_ctx {
     size_t host_batch2_bytes = 0;
     int64_t batch_notrim_shape = 0;      // (h, w, sample_ratio, mode) whose sequences once outgrew launches trimmed to the lanes in use
     PsfmBuf win_ws;                      // psfm_window_sample / psfm_result_filter workspace
+    // psfm_window_sample_batch (psfm_window_batch.hip): the selection of all windows of one call, kept between a plan call and its
+    // fill calls.  A buffer of its own: psfm_window_sample and psfm_result_filter may run in between and reuse win_ws.
+    PsfmBuf winb_ws;
+    void* winb_host = nullptr;           // pinned: the windows' first rows in the pre-cap list (65 int64)
+    struct PsfmWinbPlan {
+        bool valid = false;
+        uint64_t res_gen = 0;
+        int n_win = 0, n_frames = 0, traj_min_len = 0, min_length = 0;
+        int64_t max_num = 0;
+        int frame0[64];                          // (64 = PSFM_WINB_MAX = PSFM_DEC_BATCH_MAX windows per call)
+        uint64_t seed[64];
+        int64_t k[64];           // rows per window, after the cap
+        size_t src[64];          // where the window's ids lie in winb_ws, in bytes
+    } winb;
     PsfmBuf flt_ids, flt_birth, flt_len, flt_off, flt_xy;   // psfm_result_filter: the saved set (length >= traj_min_len), CSR
     int64_t flt_n_traj = 0, flt_n_points = 0;
     // psfm_traj_to_matches (psfm_matches.hip): keypoint / match tables of the saved set

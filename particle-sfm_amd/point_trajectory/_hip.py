@@ -29,6 +29,7 @@ EXPORTS = [
     "psfm_traj_augment", "psfm_traj_encode_weight_count", "psfm_traj_encode",
     "psfm_traj_decode_weight_count", "psfm_traj_decode_workspace_bytes", "psfm_traj_decode",
     "psfm_traj_decode_batch_workspace_bytes", "psfm_traj_decode_batch",
+    "psfm_window_sample_batch", "psfm_traj_augment_batch", "psfm_traj_encode_batch",
     "psfm_traj_eval_counts", "psfm_traj_vote_labels",
     "psfm_labels_set", "psfm_matches_to_database", "psfm_database_copy", "psfm_database_chunk_rows",
     "psfm_database_compact_again",
@@ -129,6 +130,11 @@ def lib():
     L.psfm_traj_decode_batch_workspace_bytes.argtypes = [ctypes.POINTER(i64), i32]
     L.psfm_traj_decode_batch.argtypes = [vp, i32, ctypes.POINTER(vp), ctypes.POINTER(i64), vp, vp, ctypes.c_size_t, ctypes.POINTER(vp),
                                          ctypes.POINTER(vp), ctypes.POINTER(vp), vp]
+    L.psfm_window_sample_batch.argtypes = [vp, i32, ctypes.POINTER(i32), i32, i32, i32, i64, ctypes.POINTER(ctypes.c_uint64), i32, i32, i32, i32,
+                                           i64, vp, vp, vp, vp, ctypes.POINTER(i64), vp]
+    L.psfm_traj_augment_batch.argtypes = [vp, i32, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(i64), i32, i32, i32,
+                                          vp, ctypes.POINTER(vp), vp]
+    L.psfm_traj_encode_batch.argtypes = [vp, i32, ctypes.POINTER(vp), ctypes.POINTER(vp), vp, ctypes.POINTER(i64), i32, ctypes.POINTER(vp), vp]
     L.psfm_traj_eval_counts.argtypes = [vp, vp, vp, vp, i64, vp, vp, i32, i32, i32, vp, vp]
     L.psfm_traj_vote_labels.argtypes = [vp, vp, vp, vp, i64, i32, i32, i32, vp, vp]
     L.psfm_traj_to_matches.argtypes = [vp, i32, i32, vp, ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(i64), vp]

@@ -66,6 +66,51 @@ def augment_traj_device(xy_norm, mask_absent, depth, input_hw, kinv=None, ctx=No
     return out
 
 
+def augment_windows_device(nors, masks, depths, input_hw, kinv=None, ctx=None):
+    """augment_traj_device for a list of windows of ONE n_frames through psfm_traj_augment_batch: one launch per call of at most 64
+    windows (longer lists are split).  nors[b] (K_b,L,2), masks[b] (K_b,L,1) or (K_b,L) as sample_windows_device returns them,
+    depths[b] as `_depth_stack` takes it.  Returns a list of (1,10,K_b,L) f32 views of one buffer, each bit-identical to
+    augment_traj_device on that window alone.  Asynchronous on the current stream."""
+    import ctypes
+    import torch
+    from point_trajectory import _hip
+    from .load_cut_seq import BATCH_MAX
+    ctx = ctx or _hip.context()                       # (no device: RuntimeError)
+    dev = torch.device("cuda", ctx.device)
+    h, w = int(input_hw[0]), int(input_hw[1])
+    if not (len(nors) == len(masks) == len(depths)):
+        raise ValueError("augment_windows_device: %d, %d and %d windows" % (len(nors), len(masks), len(depths)))
+    xys, mks, deps = [], [], []
+    for b, (xy_norm, mask_absent, depth) in enumerate(zip(nors, masks, depths)):
+        xy_norm, mask_absent = torch.as_tensor(xy_norm), torch.as_tensor(mask_absent)
+        if xy_norm.dim() != 3 or xy_norm.shape[2] != 2:
+            raise ValueError("augment_windows_device: window %d: xy_norm must be (K,L,2), got %s" % (b, tuple(xy_norm.shape)))
+        K, L = int(xy_norm.shape[0]), int(xy_norm.shape[1])
+        if tuple(mask_absent.shape) not in ((K, L), (K, L, 1)):
+            raise ValueError("augment_windows_device: window %d: mask_absent must be (K,L) or (K,L,1), got %s" % (b, tuple(mask_absent.shape)))
+        if xys and L != int(xys[0].shape[1]):
+            raise ValueError("augment_windows_device: the windows of one call must have one L, got %d and %d" % (int(xys[0].shape[1]), L))
+        xys.append(xy_norm.to(dev).double().contiguous())
+        mks.append(mask_absent.to(dev).double().contiguous())
+        deps.append(_depth_stack(depth, L, h, w, dev))
+    kinv = np.ascontiguousarray(reference_kinv((h, w)) if kinv is None else np.asarray(kinv, np.float32).reshape(3, 3))
+    lib, vp, out = _hip.lib(), ctypes.c_void_p, []
+    for lo in range(0, len(xys), BATCH_MAX):
+        part = xys[lo:lo + BATCH_MAX]
+        n, L = len(part), int(part[0].shape[1])
+        ks = [int(x.shape[0]) for x in part]
+        buf = torch.empty((PLANES * sum(ks) * L,), dtype=torch.float32, device=dev)        # one allocation; the windows are views of it
+        views, at = [], 0
+        for kb in ks:
+            views.append(buf[at:at + PLANES * kb * L].view(1, PLANES, kb, L))
+            at += PLANES * kb * L
+        col = lambda ts: (vp * n)(*[t.data_ptr() if t.numel() else None for t in ts])
+        _hip.check(lib.psfm_traj_augment_batch(ctx.handle, n, col(part), col(mks[lo:lo + n]), col(deps[lo:lo + n]), (ctypes.c_int64 * n)(*ks),
+                                               L, h, w, kinv.ctypes.data, col(views), _hip.current_stream_ptr(ctx.device)))
+        out += views
+    return out
+
+
 def window_features(ctx, frame0, n_frames, raw_hw, input_size, depth, traj_max_num=100000, min_length=3, traj_min_len=3, seed=0,
                     kinv=None):
     """One window from the result the last psfm_track / psfm_connect left in `ctx` to the classifier's input, on the current

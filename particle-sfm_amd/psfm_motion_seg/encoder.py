@@ -106,6 +106,56 @@ def encode_traj_device(features, mask_absent, weights, ctx=None):
     return out
 
 
+def encode_windows_device(feats, masks, weights, ctx=None):
+    """encode_traj_device for a list of windows of ONE L through psfm_traj_encode_batch: one launch per call of at most 64 windows
+    (longer lists are split).  feats[b] (1,10,K_b,L) or (10,K_b,L) fp32 as augment_windows_device returns them, masks[b] (K_b,L,1) or
+    (K_b,L).  Returns a list of (1,16,K_b) fp32 contiguous views of one buffer -- what decode_windows_device takes -- each
+    bit-identical to encode_traj_device on that window alone.  Asynchronous on the current stream."""
+    import ctypes
+    import torch
+    from point_trajectory import _hip
+    from .load_cut_seq import BATCH_MAX
+    ctx = ctx or _hip.context()                       # (no device: RuntimeError)
+    dev = torch.device("cuda", ctx.device)
+    weights = torch.as_tensor(weights)
+    if weights.numel() != WEIGHT_COUNT:
+        raise ValueError("encode_windows_device: weights has %d elements, pack_encoder_weights gives %d" % (weights.numel(), WEIGHT_COUNT))
+    if len(feats) != len(masks):
+        raise ValueError("encode_windows_device: %d feature tensors, %d masks" % (len(feats), len(masks)))
+    fts, mks = [], []
+    for b, (features, mask_absent) in enumerate(zip(feats, masks)):
+        features, mask_absent = torch.as_tensor(features), torch.as_tensor(mask_absent)
+        if features.dim() == 4 and features.shape[0] == 1:
+            features = features[0]
+        if features.dim() != 3 or features.shape[0] != N_IN:
+            raise ValueError("encode_windows_device: window %d: features must be (1,10,K,L) or (10,K,L), got %s" % (b, tuple(features.shape)))
+        K, L = int(features.shape[1]), int(features.shape[2])
+        if tuple(mask_absent.shape) not in ((K, L), (K, L, 1)):
+            raise ValueError("encode_windows_device: window %d: mask_absent must be (K,L) or (K,L,1), got %s" % (b, tuple(mask_absent.shape)))
+        if not 1 <= L <= MAX_FRAMES:
+            raise ValueError("encode_windows_device: L = %d, supported is 1 <= L <= %d (one trajectory inside one wave)" % (L, MAX_FRAMES))
+        if fts and L != int(fts[0].shape[2]):
+            raise ValueError("encode_windows_device: the windows of one call must have one L, got %d and %d" % (int(fts[0].shape[2]), L))
+        fts.append(features.to(dev).float().contiguous())
+        mks.append(mask_absent.to(dev).double().contiguous())
+    wts = weights.to(dev).float().contiguous()
+    lib, vp, out = _hip.lib(), ctypes.c_void_p, []
+    for lo in range(0, len(fts), BATCH_MAX):
+        part = fts[lo:lo + BATCH_MAX]
+        n, L = len(part), int(part[0].shape[2])
+        ks = [int(f.shape[1]) for f in part]
+        buf = torch.empty((D_MODEL * sum(ks),), dtype=torch.float32, device=dev)            # one allocation; the windows are views of it
+        views, at = [], 0
+        for kb in ks:
+            views.append(buf[at:at + D_MODEL * kb].view(1, D_MODEL, kb))
+            at += D_MODEL * kb
+        col = lambda ts: (vp * n)(*[t.data_ptr() if t.numel() else None for t in ts])
+        _hip.check(lib.psfm_traj_encode_batch(ctx.handle, n, col(part), col(mks[lo:lo + n]), _hip.ptr(wts), (ctypes.c_int64 * n)(*ks), L,
+                                              col(views), _hip.current_stream_ptr(ctx.device)))
+        out += views
+    return out
+
+
 def window_encoding(ctx, frame0, n_frames, raw_hw, input_size, depth, weights, traj_max_num=100000, min_length=3, traj_min_len=3,
                     seed=0, kinv=None):
     """One window from the result the last psfm_track / psfm_connect left in `ctx` to the encoder's output, on the current stream:

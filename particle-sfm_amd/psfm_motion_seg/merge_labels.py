@@ -182,6 +182,43 @@ def _sample_and_encode(ctx, length, window, raw_hw, input_size, traj_max_num, en
     return merger, windows
 
 
+def _sample_and_encode_batch(ctxs, lengths, window, raw_hw, input_size, traj_max_num, enc_weights, depth_ofs, seed, traj_min_len, kinv):
+    """Phase 1 of front="batch" for several contexts on one device: what _sample_and_encode returns per context, with ONE sampler
+    pass per context (load_cut_seq.sample_windows_device: one host synchronisation per 64 windows) and ONE augment and ONE encoder
+    launch per 64 windows of ALL contexts (augment.augment_windows_device, encoder.encode_windows_device).  Same saved sets, same
+    windows, same seeds, the depth maps asked for in the same order, the same bits."""
+    from point_trajectory import _hip
+    from .augment import augment_windows_device
+    from .encoder import encode_windows_device
+    from .load_cut_seq import sample_windows_device, window_ranges
+    mergers, per_ctx, flat = [], [], []
+    for ctx, length, depth_of in zip(ctxs, lengths, depth_ofs):
+        k, n = ctypes.c_int64(0), ctypes.c_int64(0)
+        _hip.check(_hip.lib().psfm_result_filter(ctx.handle, int(traj_min_len), ctypes.byref(k), ctypes.byref(n), _hip.current_stream_ptr(ctx.device)))
+        mergers.append(LabelMerger(ctx))
+        ranges = window_ranges(length, window)
+        sampled = sample_windows_device(ctx, ranges, raw_hw, input_size, traj_max_num, 3, traj_min_len, [seed + w for w in range(len(ranges))])
+        windows = [[f0, nf, ids, None, mask] for (f0, nf), (ids, raw, nor, mask) in zip(ranges, sampled)]
+        flat += [(win, nor, depth_of(np.arange(f0, f0 + nf))) for win, (f0, nf), (_, _, nor, _) in zip(windows, ranges, sampled)]
+        per_ctx.append(windows)
+    lo = 0
+    while lo < len(flat):           # (a sequence shorter than the window has windows of its own length: runs of one n_frames)
+        hi = lo
+        while hi < len(flat) and flat[hi][0][1] == flat[lo][0][1]:
+            hi += 1
+        run = flat[lo:hi]
+        feats = augment_windows_device([r[1] for r in run], [r[0][4] for r in run], [r[2] for r in run], input_size, kinv=kinv, ctx=ctxs[0])
+        for r, enc in zip(run, encode_windows_device(feats, [r[0][4] for r in run], enc_weights, ctx=ctxs[0])):
+            r[0][3] = enc
+        lo = hi
+    return mergers, [[tuple(win) for win in windows] for windows in per_ctx]
+
+
+def _check_front(front):
+    if front not in ("window", "batch"):
+        raise ValueError("front must be \"window\" or \"batch\", got %r" % (front,))
+
+
 def decode_groups(rows, max_rows=None):
     """Consecutive windows with `rows` trajectories each -> [(first, last + 1), ...]: a group closes before the window that would take
     it above max_rows (default DEFAULT_MAX_ROWS); a window larger than that stands alone."""
@@ -216,7 +253,7 @@ def _decode_and_merge(mergers, windows_per_ctx, dec_weights, ctx, max_rows):
 
 
 def label_trajectories_batched(length, window, raw_hw, input_size, traj_max_num, enc_weights, dec_weights, depth_for_window, seed=0,
-                               traj_min_len=3, kinv=None, ctx=None, max_rows=None):
+                               traj_min_len=3, kinv=None, ctx=None, max_rows=None, front="window"):
     """label_trajectories(..., predict=decoder.device_predictor(enc_weights, dec_weights, depth_for_window, input_size, kinv, ctx))
     with the decoder run once per GROUP of windows instead of once per window: the same saved set, the same windows
     (load_cut_seq.window_ranges), the same seeds (seed + w), the same merger, the same bytes out of finish().
@@ -226,28 +263,42 @@ def label_trajectories_batched(length, window, raw_hw, input_size, traj_max_num,
          default DEFAULT_MAX_ROWS, so that the group's workspace, 2.6 KB per row, stays bounded).  A window's result is that of
          psfm_traj_decode on the window alone, so the grouping changes no bit;
       3. LabelMerger.add_window in window order, then finish().
+    front="batch" runs step 1 for all windows at once -- load_cut_seq.sample_windows_device, augment.augment_windows_device,
+    encoder.encode_windows_device: one sampler pass with one host synchronisation, one augment and one encoder launch per 64
+    windows -- with the same bytes out of finish(); the default "window" is the per-window loop.
     Returns the merger, finished, with `window_ids`."""
     from point_trajectory import _hip
+    _check_front(front)
     ctx = ctx or _hip.context()
-    merger, windows = _sample_and_encode(ctx, length, window, raw_hw, input_size, traj_max_num, enc_weights, depth_for_window, seed,
-                                         traj_min_len, kinv)
+    if front == "batch":
+        (merger,), (windows,) = _sample_and_encode_batch([ctx], [length], window, raw_hw, input_size, traj_max_num, enc_weights,
+                                                         [depth_for_window], seed, traj_min_len, kinv)
+    else:
+        merger, windows = _sample_and_encode(ctx, length, window, raw_hw, input_size, traj_max_num, enc_weights, depth_for_window, seed,
+                                             traj_min_len, kinv)
     _decode_and_merge([merger], [windows], dec_weights, ctx, max_rows)
     return merger
 
 
 def label_sequences_batched(ctxs, lengths, window, raw_hw, input_size, traj_max_num, enc_weights, dec_weights, depth_for_window, seed=0,
-                            traj_min_len=3, kinv=None, max_rows=None):
+                            traj_min_len=3, kinv=None, max_rows=None, front="window"):
     """label_trajectories_batched for several contexts on one device -- what trajectory.run_connect_batch returns -- with the windows
     of ALL sequences going through the same decode groups: sequence after sequence, window after window.  lengths[i]: frames of
     sequence i; depth_for_window(seq_index, time_idx).  Sampling, augment and encode (phase 1) and the merge (phase 3) stay per context;
-    every context's labelled set equals what label_trajectories_batched gives for it alone.  Returns the finished mergers."""
+    every context's labelled set equals what label_trajectories_batched gives for it alone.  front="batch": the sampler runs one
+    pass per context (every context has its own result), augment and encoder run over the windows of ALL contexts in one launch each
+    per 64 windows; the same bytes.  Returns the finished mergers."""
+    _check_front(front)
     ctxs = list(ctxs)
     if len(ctxs) != len(lengths):
         raise ValueError("label_sequences_batched: %d contexts, %d lengths" % (len(ctxs), len(lengths)))
     if any(c.device != ctxs[0].device for c in ctxs):
         raise ValueError("label_sequences_batched: the contexts must be on one device")
     mergers, per_ctx = [], []
-    for i, (ctx, length) in enumerate(zip(ctxs, lengths)):
+    if front == "batch" and ctxs:
+        mergers, per_ctx = _sample_and_encode_batch(ctxs, [int(n) for n in lengths], window, raw_hw, input_size, traj_max_num, enc_weights,
+                                                    [lambda t, i=i: depth_for_window(i, t) for i in range(len(ctxs))], seed, traj_min_len, kinv)
+    for i, (ctx, length) in enumerate(zip(ctxs, lengths) if front == "window" else []):
         merger, windows = _sample_and_encode(ctx, int(length), window, raw_hw, input_size, traj_max_num, enc_weights,
                                              lambda t, i=i: depth_for_window(i, t), seed, traj_min_len, kinv)
         mergers.append(merger)
