@@ -613,6 +613,37 @@ psfm_status psfm_labels_copy(psfm_ctx* ctx, int32_t* ids_out, int64_t* off_out, 
                              uint8_t* labels_out, void* stream);
 psfm_status psfm_labels_to_matches(psfm_ctx* ctx, int n_img, int sample_k, int remove_dynamic, int64_t* n_kp_host,
                                    int64_t* n_matches_host, int64_t* n_pairs_host, void* stream);
+/* the sizes of the labelled set in the context (PSFM_ERR_ARG: none); either may be NULL.  No device work. */
+psfm_status psfm_labels_sizes(psfm_ctx* ctx, int64_t* n_traj, int64_t* n_points);
+
+/* The saved sets and the match tables of n_seq = 1 .. 64 sequences in ONE pass each: psfm_result_filter, psfm_traj_to_matches and
+ * psfm_labels_to_matches for every context of a batch (psfm_connect_batch / label_sequences_batched leave one context per
+ * sequence), with a number of host synchronisations (at most 2 for the filter, at most 4 for the tables: the single calls') and of
+ * launches that does not depend on n_seq.  No new rule: afterwards context b is in exactly the state the single call
+ * (ctxs[b], ..., n_img[b], labels_dev[b]) leaves -- the saved set / the tables byte for byte, the counts, res_gen -- so
+ * psfm_result_filtered_copy, psfm_matches_copy, psfm_matches_to_database and everything behind them run unchanged, context by
+ * context.  The contexts are distinct, non-NULL and on one device; ctxs[0] owns the call's shared workspace (the intermediates of
+ * all sequences live once, there).  All *_host arguments are arrays of n_seq entries.
+ *   psfm_result_filter_batch      n_traj_host / n_points_host [n_seq]
+ *   psfm_traj_to_matches_batch    over the saved sets; n_img [n_seq] may differ per sequence and exceed the frames present;
+ *                                 labels_dev: NULL, or [n_seq] DEVICE arrays as in psfm_traj_to_matches, NULL entries allowed
+ *   psfm_labels_to_matches_batch  over the labelled sets (every context needs one: psfm_labels_finish / psfm_labels_set)
+ * A sequence that turns out empty gets its empty state (the zero-filled kp_off of n_img[b] + 1 entries included); the others go on.
+ * PSFM_ERR_ARG before anything is launched, with every context untouched (tables of an earlier call still copy out) and
+ * psfm_last_error() naming the first offending sequence: n_seq out of range; a NULL, repeated or foreign-device context;
+ * n_img[b] < 1; sample_k < 1; no labelled set; 2^32 - 1 or more points (2^31 - 1 or more trajectories for the filter) over all
+ * sequences; a sort key (sequence, src * n_img + tgt) that does not fit 64 bits.  PSFM_ERR_ARG found on the device: a frame outside
+ * [0, n_img[b]) -- never used as an index -- names the lowest such sequence and leaves EVERY context of the call with empty tables
+ * (all counts 0).  Two identical calls give identical bytes.
+ *   psfm_matches_batch_census     for the last of these calls that ctx0 owned: its host synchronisations and the library's own
+ *                                 launches, copies and memsets (not what rocPRIM launches inside a sort or a scan). */
+psfm_status psfm_result_filter_batch(psfm_ctx* const* ctxs, int n_seq, int traj_min_len, int64_t* n_traj_host, int64_t* n_points_host,
+                                     void* stream);
+psfm_status psfm_traj_to_matches_batch(psfm_ctx* const* ctxs, int n_seq, const int* n_img, int sample_k, const uint8_t* const* labels_dev,
+                                       int64_t* n_kp_host, int64_t* n_matches_host, int64_t* n_pairs_host, void* stream);
+psfm_status psfm_labels_to_matches_batch(psfm_ctx* const* ctxs, int n_seq, const int* n_img, int sample_k, int remove_dynamic,
+                                         int64_t* n_kp_host, int64_t* n_matches_host, int64_t* n_pairs_host, void* stream);
+psfm_status psfm_matches_batch_census(psfm_ctx* ctx0, int32_t* host_syncs, int32_t* launches);
 
 /* sfm/import_feature_matches.py:76-104 (import_keypoints_matches) writing through sfm/colmap_utils/database.py:181-225: the match
  * tables that the last psfm_traj_to_matches / psfm_labels_to_matches left in the context become the blobs of the COLMAP database's

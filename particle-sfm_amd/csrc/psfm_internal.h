@@ -229,6 +229,12 @@ struct psfm_ctx {
     PsfmBuf mt_kp_off, mt_q, mt_pts, mt_kp_ind, mt_kp_xy, mt_moff, mt_keys, mt_rows, mt_gid, mt_pairs;
     int64_t mt_n_kp = 0, mt_n_m = 0, mt_n_pairs = 0;
     int mt_n_img = 0;
+    // psfm_result_filter_batch / psfm_*_to_matches_batch (psfm_matches_batch.hip), this context as the call's owner: the table of
+    // sequences, the per-sequence sizes and flags a synchronisation reads back, the filter's kept lengths; their pinned staging; the
+    // census of the last call (psfm_matches_batch_census)
+    PsfmBuf mtb_tab, mtb_sizes, mtb_len;
+    void* mtb_host = nullptr;
+    int32_t mtb_syncs = 0, mtb_launches = 0;
     // psfm_labels_* (psfm_labels.hip): per-window motion labels merged over the saved set, and the labelled set built from them
     uint64_t res_gen = 0;                // bumped by every entry point that replaces the result or the saved set (psfm_track, psfm_connect,
                                          // psfm_connect_batch, psfm_result_filter): what psfm_labels_begin ties its state to

@@ -20,19 +20,9 @@
 
 #include "psfm_device.h"
 #include "psfm_internal.h"
+#include "psfm_matches_batch.h"      // the rules of one sequence, shared with the batched kernels (psfm_matches_batch.hip)
 
 #define PM_BLOCK 256
-
-// owner trajectory of flat point p: the last t with off[t] <= p
-__device__ __forceinline__ int pm_owner(const int64_t* __restrict__ off, int64_t k, int64_t p)
-{
-    int64_t lo = 0, hi = k;            // off[lo] <= p < off[hi]
-    while (hi - lo > 1) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (off[mid] <= p) lo = mid; else hi = mid;
-    }
-    return (int)lo;
-}
 
 __global__ __launch_bounds__(PM_BLOCK) void pm_keep_kernel(const uint8_t* __restrict__ labels, int64_t n_pts, int64_t* __restrict__ keep)
 {
@@ -52,13 +42,14 @@ __global__ __launch_bounds__(PM_BLOCK) void pm_compact_kernel(const uint8_t* __r
     const int64_t p = (int64_t)blockIdx.x * PM_BLOCK + threadIdx.x;
     if (p >= n_pts || (labels && labels[p] != 0)) return;
     const int64_t q = q_of[p];
-    const int t = pm_owner(off, k, p);
-    const int f = frames ? frames[p] : birth[t] + (int)(p - off[t]);    // explicit frames (the labelled set) or birth + offset
+    const int t = psfm_mt_owner(off, k, p);
+    const int f = psfm_mt_frame(frames, birth, off, t, p);             // explicit frames (the labelled set) or birth + offset
     // a frame outside the image list is an argument error, reported by the host once this pass is over; the entry is still
     // written (frame 0) -- the sort and the kernels behind it run before the host looks at the flag and must stay in bounds
-    const bool outside = f < 0 || f >= n_img;
+    bool outside;
+    const unsigned fi = psfm_mt_frame_index(f, n_img, &outside);
     if (outside) *bad = 1;
-    kfr[q] = outside ? 0u : (unsigned)f;
+    kfr[q] = fi;
     kpt[q] = p;
     ktraj[q] = t;
     iota[q] = (unsigned)q;
@@ -69,12 +60,7 @@ __global__ __launch_bounds__(PM_BLOCK) void pm_kp_off_kernel(const unsigned* __r
 {
     const int i = blockIdx.x * PM_BLOCK + threadIdx.x;
     if (i > n_img) return;
-    int64_t lo = 0, hi = n_kept;       // first s with fsorted[s] >= i
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (fsorted[mid] < (unsigned)i) lo = mid + 1; else hi = mid;
-    }
-    kp_off[i] = lo;
+    kp_off[i] = psfm_mt_lower_bound<unsigned>(fsorted, 0, n_kept, ~0u, (unsigned)i);       // first s with fsorted[s] >= i
 }
 
 // s-th point of the frame-sorted order: keypoint index of its point, its coordinates; and how many matches the point emits
@@ -100,14 +86,7 @@ __global__ __launch_bounds__(PM_BLOCK) void pm_count_kernel(const int* __restric
     if (q == n_kept) { m_cnt[q] = 0; return; }
     const int t = ktraj[q];
     const int64_t t0 = q_of[off[t]];
-    const int64_t n = q_of[off[t + 1]] - t0, j = q - t0;
-    int64_t m;
-    if (n <= sample_k) m = n - 1;
-    else {
-        const int64_t stride = n / sample_k;
-        m = sample_k - ((j % stride == 0 && j / stride < sample_k) ? 1 : 0);
-    }
-    m_cnt[q] = m;
+    m_cnt[q] = psfm_mt_match_count(q_of[off[t + 1]] - t0, q - t0, sample_k);
 }
 
 __global__ __launch_bounds__(PM_BLOCK) void pm_emit_kernel(const int* __restrict__ ktraj, const int64_t* __restrict__ q_of,
@@ -122,7 +101,8 @@ __global__ __launch_bounds__(PM_BLOCK) void pm_emit_kernel(const int* __restrict
     const int t = ktraj[q];
     const int64_t t0 = q_of[off[t]];
     const int64_t n = q_of[off[t + 1]] - t0, j = q - t0;
-    const int64_t reps = n <= sample_k ? n : sample_k, stride = n <= sample_k ? 1 : n / sample_k;
+    int64_t reps, stride;
+    psfm_mt_targets(n, sample_k, &reps, &stride);
     int64_t e = m_off[q];
     const unsigned long long fsrc = kfr[q];
     const int ksrc = kp_ind[q];

@@ -16,6 +16,7 @@
 
 #include "psfm_device.h"
 #include "psfm_internal.h"
+#include "psfm_matches_batch.h"      // the rules of the saved set, shared with psfm_result_filter_batch
 
 #define PW_BLOCK 256
 
@@ -168,7 +169,7 @@ __global__ __launch_bounds__(PW_BLOCK) void psfm_filter_flag_kernel(const int* _
 {
     const int64_t i = (int64_t)blockIdx.x * PW_BLOCK + threadIdx.x;
     if (i >= n) return;
-    flag[i] = (uint8_t)(len[i] >= min_len);
+    flag[i] = (uint8_t)psfm_flt_keep(len[i], min_len);
     iota[i] = (int)i;
 }
 __global__ __launch_bounds__(PW_BLOCK) void psfm_filter_meta_kernel(const int* __restrict__ ids, int64_t k, const int* __restrict__ birth,
@@ -178,10 +179,7 @@ __global__ __launch_bounds__(PW_BLOCK) void psfm_filter_meta_kernel(const int* _
     const int64_t i = (int64_t)blockIdx.x * PW_BLOCK + threadIdx.x;
     if (i > k) return;
     if (i == k) { len64[i] = 0; return; }
-    const int id = ids[i];
-    birth_out[i] = birth[id];
-    len_out[i] = len[id];
-    len64[i] = (int64_t)len[id];
+    psfm_flt_meta(ids[i], i, birth, len, birth_out, len_out, len64);
 }
 __global__ __launch_bounds__(PW_BLOCK) void psfm_filter_copy_kernel(const int* __restrict__ ids, int64_t k, const int* __restrict__ len,
                                                                   const int64_t* __restrict__ off, const int64_t* __restrict__ off_out,
@@ -193,7 +191,7 @@ __global__ __launch_bounds__(PW_BLOCK) void psfm_filter_copy_kernel(const int* _
         const int id = ids[t];
         const int n = len[id];
         const int64_t src = off[id], dst = off_out[t];
-        for (int j = lane; j < n; j += PSFM_WAVE) xy_out[dst + j] = xy[src + j];
+        psfm_flt_copy_run(xy, src, xy_out, dst, n, lane, PSFM_WAVE);
     }
 }
 

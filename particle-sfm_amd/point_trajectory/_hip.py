@@ -38,6 +38,7 @@ EXPORTS = [
     "psfm_ctx_set_motion_boundary", "psfm_motion_boundary", "psfm_kill_map",
     "psfm_depth_display", "psfm_ctx_set_depth_display", "psfm_depth_display_last_ms", "psfm_depth_display_chunk",
     "psfm_track_queries", "psfm_track_queries_optimize",
+    "psfm_result_filter_batch", "psfm_traj_to_matches_batch", "psfm_labels_to_matches_batch", "psfm_matches_batch_census", "psfm_labels_sizes",
 ]
 
 
@@ -146,6 +147,13 @@ def lib():
     L.psfm_labels_copy.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.psfm_labels_to_matches.argtypes = [vp, i32, i32, i32, ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(i64), vp]
     L.psfm_labels_set.argtypes = [vp, i64, i64, vp, vp, vp, vp, vp, vp]
+    L.psfm_labels_sizes.argtypes = [vp, ctypes.POINTER(i64), ctypes.POINTER(i64)]
+    L.psfm_result_filter_batch.argtypes = [ctypes.POINTER(vp), i32, i32, ctypes.POINTER(i64), ctypes.POINTER(i64), vp]
+    L.psfm_traj_to_matches_batch.argtypes = [ctypes.POINTER(vp), i32, ctypes.POINTER(i32), i32, ctypes.POINTER(vp), ctypes.POINTER(i64),
+                                             ctypes.POINTER(i64), ctypes.POINTER(i64), vp]
+    L.psfm_labels_to_matches_batch.argtypes = [ctypes.POINTER(vp), i32, ctypes.POINTER(i32), i32, i32, ctypes.POINTER(i64),
+                                               ctypes.POINTER(i64), ctypes.POINTER(i64), vp]
+    L.psfm_matches_batch_census.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32)]
     L.psfm_matches_to_database.argtypes = [vp, i32, vp, vp, ctypes.POINTER(i64), ctypes.POINTER(i64), vp]
     L.psfm_database_copy.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.psfm_database_chunk_rows.argtypes = []

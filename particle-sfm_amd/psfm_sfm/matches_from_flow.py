@@ -198,3 +198,142 @@ def traj_to_matches_labelled_device(ctx, image_names, match_list_file, remove_dy
     track.npy round trip), assembled like the host path."""
     tables = match_tables_labelled_device(ctx, len(image_names), remove_dynamic, sample_k)
     return assemble(list(image_names), tables, match_list_file, as_arrays)
+
+
+# ---- all sequences of a batch in one pass (csrc/psfm_matches_batch.hip) -------------------------------------------------------------
+BATCH_MAX = 64          # sequences per call: PSFM_BATCH_MAX
+# Points per batched call.  In the worst case every point emits sample_k = 20 matches of 40 bytes of scratch each: 2^25 points are
+# 27 GB, under the 48 GiB BATCH_BYTES of point_trajectory/batch.py.  (The scratch itself is sized from the counted matches.)
+MAX_POINTS = 1 << 25
+
+
+def group_sequences(n_points, max_points=MAX_POINTS, max_seq=BATCH_MAX):
+    """The grouping rule of the batched calls (psfm_mtb_group_end of csrc/psfm_matches_batch.h): the list is cut into consecutive
+    groups of at most `max_seq` sequences and at most `max_points` points; a sequence above the cap is a group of its own and goes
+    through the single entry points.  Returns [(start, end, alone)]."""
+    out, i, n = [], 0, len(n_points)
+    while i < n:
+        if n_points[i] > max_points:
+            out.append((i, i + 1, True))
+            i += 1
+            continue
+        e, total = i, 0
+        while e < n and e - i < max_seq and n_points[e] <= max_points and total + n_points[e] <= max_points:
+            total += n_points[e]
+            e += 1
+        out.append((i, e, False))
+        i = e
+    return out
+
+
+def _handles(ctxs):
+    import ctypes
+    if len({c.device for c in ctxs}) > 1:
+        raise ValueError("the contexts of a batch must be on one device")
+    return (ctypes.c_void_p * len(ctxs))(*[c.handle.value for c in ctxs])
+
+
+def result_filter_batch_device(ctxs, traj_min_len=3):
+    """psfm_result_filter for every context, at most 64 per call: [(n_traj, n_points)] in the order given."""
+    import ctypes
+    from point_trajectory import _hip
+    L = _hip.lib()
+    out = []
+    for lo in range(0, len(ctxs), BATCH_MAX):
+        part = ctxs[lo:lo + BATCH_MAX]
+        k, npt = (ctypes.c_int64 * len(part))(), (ctypes.c_int64 * len(part))()
+        _hip.check(L.psfm_result_filter_batch(_handles(part), len(part), int(traj_min_len), k, npt, _hip.current_stream_ptr(part[0].device)))
+        out += [(int(k[i]), int(npt[i])) for i in range(len(part))]
+    return out
+
+
+def _tables_batch(ctxs, n_imgs, n_points, max_points, single, batch):
+    """Groups by the grouping rule; `single(i)` / `batch(lo, hi, handles, n_img, kp, m, p, stream)` run the entry points; then one
+    psfm_matches_copy per context."""
+    import ctypes
+    from point_trajectory import _hip
+    tables = []
+    for lo, hi, alone in group_sequences(n_points, max_points):
+        if alone:
+            sizes = [single(lo)]
+        else:
+            part = ctxs[lo:hi]
+            n = hi - lo
+            kp, m, p = (ctypes.c_int64 * n)(), (ctypes.c_int64 * n)(), (ctypes.c_int64 * n)()
+            n_img = (ctypes.c_int32 * n)(*[int(v) for v in n_imgs[lo:hi]])
+            _hip.check(batch(lo, hi, _handles(part), n_img, kp, m, p, _hip.current_stream_ptr(part[0].device)))
+            sizes = [(int(kp[i]), int(m[i]), int(p[i])) for i in range(n)]
+        tables += [_copy_tables(ctxs[lo + i], int(n_imgs[lo + i]), *sizes[i]) for i in range(hi - lo)]
+    return tables
+
+
+def match_tables_batch_device(ctxs, n_imgs, traj_min_len=3, sample_k=SAMPLE_K, labels=None, max_points=MAX_POINTS):
+    """match_tables_device for every context of a batch (psfm_connect_batch leaves one per sequence): the saved sets through
+    psfm_result_filter_batch, the tables through psfm_traj_to_matches_batch -- host synchronisations and launches per call that do
+    not depend on the number of sequences -- then one copy of the finished tables per context.  labels: None, or one entry per
+    sequence (a uint8 device tensor over the saved set's points, or None).  Returns the table tuples in the order given, equal
+    to the per-sequence function's."""
+    import ctypes
+    from point_trajectory import _hip
+    L = _hip.lib()
+    ctxs, labels = list(ctxs), (None if labels is None else list(labels))
+    if len(n_imgs) != len(ctxs) or (labels is not None and len(labels) != len(ctxs)):
+        raise ValueError("one n_img (and one labels entry) per context")
+    n_points = [n for _, n in result_filter_batch_device(ctxs, traj_min_len)]
+
+    def single(i):
+        a, b, c = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        _hip.check(L.psfm_traj_to_matches(ctxs[i].handle, int(n_imgs[i]), int(sample_k), _hip.ptr(None if labels is None else labels[i]),
+                                          ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), _hip.current_stream_ptr(ctxs[i].device)))
+        return int(a.value), int(b.value), int(c.value)
+
+    def batch(lo, hi, handles, n_img, kp, m, p, sp):
+        lab = None
+        if labels is not None:
+            lab = (ctypes.c_void_p * (hi - lo))(*[_hip.ptr(t).value for t in labels[lo:hi]])
+        return L.psfm_traj_to_matches_batch(handles, hi - lo, n_img, int(sample_k), lab, kp, m, p, sp)
+
+    return _tables_batch(ctxs, n_imgs, n_points, max_points, single, batch)
+
+
+def match_tables_labelled_batch_device(ctxs, n_imgs, remove_dynamic=True, sample_k=SAMPLE_K, max_points=MAX_POINTS):
+    """match_tables_labelled_device for every context of a batch (label_sequences_batched leaves a labelled set in each): the tables
+    through psfm_labels_to_matches_batch, then one copy per context.  Returns the table tuples in the order given."""
+    import ctypes
+    from point_trajectory import _hip
+    L = _hip.lib()
+    ctxs = list(ctxs)
+    if len(n_imgs) != len(ctxs):
+        raise ValueError("one n_img per context")
+    n_points = []
+    for c in ctxs:
+        n = ctypes.c_int64(0)
+        _hip.check(L.psfm_labels_sizes(c.handle, None, ctypes.byref(n)))
+        n_points.append(int(n.value))
+    rd = 1 if remove_dynamic else 0
+
+    def single(i):
+        a, b, c = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        _hip.check(L.psfm_labels_to_matches(ctxs[i].handle, int(n_imgs[i]), int(sample_k), rd, ctypes.byref(a), ctypes.byref(b),
+                                            ctypes.byref(c), _hip.current_stream_ptr(ctxs[i].device)))
+        return int(a.value), int(b.value), int(c.value)
+
+    def batch(lo, hi, handles, n_img, kp, m, p, sp):
+        return L.psfm_labels_to_matches_batch(handles, hi - lo, n_img, int(sample_k), rd, kp, m, p, sp)
+
+    return _tables_batch(ctxs, n_imgs, n_points, max_points, single, batch)
+
+
+def traj_to_matches_batch_device(ctxs, image_names, match_list_files, traj_min_len=3, sample_k=SAMPLE_K, labels=None, as_arrays=True,
+                                 max_points=MAX_POINTS):
+    """traj_to_matches_device for every sequence of a batch: image_names and match_list_files hold one entry per sequence.  Returns
+    the `assemble` results in the order given."""
+    tables = match_tables_batch_device(ctxs, [len(n) for n in image_names], traj_min_len, sample_k, labels, max_points)
+    return [assemble(list(n), t, f, as_arrays) for n, t, f in zip(image_names, tables, match_list_files)]
+
+
+def traj_to_matches_labelled_batch_device(ctxs, image_names, match_list_files, remove_dynamic=True, sample_k=SAMPLE_K, as_arrays=True,
+                                          max_points=MAX_POINTS):
+    """traj_to_matches_labelled_device for every sequence of a batch.  Returns the `assemble` results in the order given."""
+    tables = match_tables_labelled_batch_device(ctxs, [len(n) for n in image_names], remove_dynamic, sample_k, max_points)
+    return [assemble(list(n), t, f, as_arrays) for n, t, f in zip(image_names, tables, match_list_files)]
