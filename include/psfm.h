@@ -129,7 +129,9 @@ psfm_status psfm_ctx_set_chain_mode(psfm_ctx* ctx, int mode);
  *     the occlusion and motion-boundary masks travel as one byte per pixel in a stack owned by the context, built by one launch
  *     from the flows and the COMPLETE occlusion maps -- `occ` of the caller stays 0/1;
  *   - track_optimize runs a frame as two launches (chain step, then the solve in any of its forms);
- *   - psfm_connect_batch and psfm_shard_begin refuse the context (PSFM_ERR_ARG). */
+ *   - psfm_connect_batch takes a batch whose contexts ALL have the option on (each context's own thres is honoured; its frame launches
+ *     carry the second verdict, info->chain_mode == 3) and refuses one whose contexts disagree (PSFM_ERR_ARG);
+ *   - psfm_shard_begin refuses the context (PSFM_ERR_ARG). */
 psfm_status psfm_ctx_set_motion_boundary(psfm_ctx* ctx, int enable, float thres);
 
 /* trajectory.py:39-43 for a stack of flow maps: mb_out[f,y,x] = 1 where the flow gradient of pixel (x, y) of map f exceeds
@@ -143,6 +145,19 @@ psfm_status psfm_motion_boundary(psfm_ctx* ctx, const float* flows, int n, int h
  * Asynchronous on `stream`. */
 psfm_status psfm_kill_map(psfm_ctx* ctx, const float* flows, const uint8_t* occ, int n, int h, int w, float thres, uint8_t* kill_out,
                           void* stream);
+
+/* psfm_kill_map for n_seq (1..64) stacks of the SAME frame size in ONE launch, restricted to frames [pair0, pair0 + n_pairs) of every
+ * stack: what psfm_connect_batch enqueues behind each chunk of flow_check when its contexts have the option on.
+ *   flows[i] (n_flows[i],H,W,2) f32, occ[i] / kill_out[i] (n_flows[i],H,W) u8, thres[i]: stack i's own threshold
+ * A stack with fewer frames than pair0 + n_pairs is touched only where it has frames.  Every byte written equals psfm_kill_map's on
+ * that stack alone.  The range is a contract: the call reads the occlusion bytes of the frames of the range only and writes the kill
+ * bytes of exactly those frames; the flows it uses are those frames' (it may LOAD flow values of the following frame of the same
+ * stack that it never uses, never anything outside the stack).  The frames outside the range may therefore be unwritten or in
+ * production while the call runs.  PSFM_ERR_ARG, with nothing written: a NULL pointer (an array or one of its entries), n_seq outside
+ * 1..64, a bad frame size, a negative n_flows[i], a negative or non-finite threshold, pair0 < 0 or n_pairs < 0.
+ * `ctx` keeps the table of stacks.  Asynchronous on `stream`. */
+psfm_status psfm_kill_map_batch(psfm_ctx* ctx, const float* const* flows, const uint8_t* const* occ, const int* n_flows, int n_seq, int h,
+                                int w, const float* thres, int pair0, int n_pairs, uint8_t* const* kill_out, void* stream);
 
 /* How psfm_track / psfm_connect run the path-consistency solve of a frame (track_optimize.py:49-50 ->
  * trajectory_optimize.cpp:74-82) -- the results do not depend on it:
@@ -335,7 +350,11 @@ psfm_status psfm_track_queries_optimize(psfm_ctx* ctx, const float* flows_f, con
  * a whole window of it is like that (or its context is set to the launch chain, psfm_ctx_set_solver mode 1) it leaves the batch
  * and is run alone by psfm_connect behind it.  Ids, lengths and every solver decision do not depend on the batching; track-mode positions are bit-identical, path-consistency
  * positions agree to rounding (<= 1e-9 px: a sequence that leaves the batch solves on a share of the block slots, see
- * psfm_ctx_set_resident_budget).  n_seq <= 64.  Synchronises `stream`. */
+ * psfm_ctx_set_resident_budget).  n_seq <= 64.  Synchronises `stream`.
+ * Motion boundary (psfm_ctx_set_motion_boundary): on in EVERY context of the batch, each with its own threshold, or in none; contexts
+ * that disagree are PSFM_ERR_ARG.  With it on every frame launch forms the second verdict from the sequences' kill maps, which are
+ * built for all sequences together (psfm_kill_map_batch's launch) behind each chunk of flow_check; results are those of psfm_connect
+ * with the option on, sequence by sequence, and info->chain_mode is 3 for a sequence that stayed in the batch. */
 psfm_status psfm_connect_batch(psfm_ctx* const* ctxs, int n_seq, const float* const* flows_f, const float* const* flows_b,
                                const float* const* flows_f2, const float* const* flows_b2, const int* n_flows, int h, int w,
                                float thres, int sample_ratio, psfm_track_info* infos_host, void* stream);

@@ -17,6 +17,9 @@
 //     (psfm_finalize_batch: one sort over the records of all sequences);
 //   * a sequence whose solves reject steps (what the launch chain / the resident solve are for) is redone at the checkpoint like in
 //     psfm_track; when a whole window of it is like that it leaves the batch and runs alone through psfm_connect afterwards.
+//   * psfm_ctx_set_motion_boundary on EVERY context of the batch: the frame launches are the MB forms of the two kernels
+//     (psfm_motion_boundary.hip, psfm_solver_batch_mb.hip) and sample every sequence's kill maps (c->kill), built by ONE launch per
+//     flow_check chunk for all sequences (psfm_kill_map_batch_kernel); contexts that disagree are refused.
 // Results are those of psfm_connect, sequence by sequence (tests/test_gpu_batch.py: bit-identical to the oracle's).
 #include <string.h>
 #include <stdlib.h>
@@ -77,9 +80,10 @@ extern "C" psfm_status psfm_connect_batch(psfm_ctx* const* ctxs, int n_seq, cons
     for (int i = 0; i < n_seq; ++i) if (ctxs[i]) ctxs[i]->res_gen++;
     for (int i = 0; i < n_seq; ++i) {
         if (!ctxs[i] || ctxs[i]->device != ctxs[0]->device) { psfm_set_error("psfm_connect_batch: context %d is NULL or on another device", i); return PSFM_ERR_ARG; }
-        if (ctxs[i]->mb_enable) {
-            psfm_set_error("psfm_connect_batch: context %d has psfm_ctx_set_motion_boundary on; the batched frame launches do not form the "
-                           "motion-boundary verdict -- run its sequence through psfm_connect", i);
+        if (ctxs[i]->mb_enable != ctxs[0]->mb_enable) {      // (one kernel form per launch: all sequences with the second verdict, or none)
+            psfm_set_error("psfm_connect_batch: context %d has psfm_ctx_set_motion_boundary %s and context 0 has it %s; a batch takes the option "
+                           "on every context or on none (each with its own threshold)", i, ctxs[i]->mb_enable ? "on" : "off",
+                           ctxs[0]->mb_enable ? "on" : "off");
             return PSFM_ERR_ARG;
         }
         for (int j = 0; j < i; ++j) if (ctxs[j] == ctxs[i]) { psfm_set_error("psfm_connect_batch: context %d given twice (one per sequence)", i); return PSFM_ERR_ARG; }
@@ -100,7 +104,8 @@ extern "C" psfm_status psfm_connect_batch(psfm_ctx* const* ctxs, int n_seq, cons
     // (the counters a failed finalize reads the "grid too small" bit from are the ones THIS call refreshes: none left over from an earlier one)
     for (int i = 0; i < n_seq; ++i) if (ctxs[i]->host_pinned) ((PsfmCounters*)ctxs[i]->host_pinned)->overflow = 0;
     // A failed run leaves nothing in flight that still reads the caller's flow stacks or writes the maps: the side stream's flow_check
-    // launches are drained before the error goes back (the caller may free or reuse the tensors), and before the untrimmed rerun.
+    // launches (and, with the motion-boundary option, the kill-map launches behind them) are drained before the error goes back (the
+    // caller may free or reuse the tensors), and before the untrimmed rerun.
     auto quiesce = [&]() {
         if (hipSetDevice(own0->device) != hipSuccess) return;
         if (own0->side_stream) (void)hipStreamSynchronize(own0->side_stream);
@@ -130,6 +135,7 @@ static psfm_status batch_run(psfm_ctx* const* ctxs, int n_seq, const float* cons
     const bool optimize = flows_f2 != nullptr;
     *grid_too_small = false;
     psfm_ctx* own = ctxs[0];
+    const bool mb = own->mb_enable;      // psfm_ctx_set_motion_boundary, on in every context of the batch: the frame launches sample kill maps
     PSFM_HIP(hipSetDevice(own->device));
     hipStream_t s = (hipStream_t)stream;
     const int B = n_seq;
@@ -162,6 +168,7 @@ static psfm_status batch_run(psfm_ctx* const* ctxs, int n_seq, const float* cons
             if (D[i].shift_d + tbits > 63) { psfm_set_error("psfm_connect_batch: key does not fit 64 bits"); return PSFM_ERR_ARG; }
             if ((st = psfm_track_alloc(c, D[i])) != PSFM_OK) return st;
             if ((st = c->occ_own.ensure((size_t)P * (size_t)n_flows[i])) != PSFM_OK) return st;
+            if (mb && (st = c->kill.ensure((size_t)P * (size_t)n_flows[i])) != PSFM_OK) return st;
             if (optimize) {
                 if ((st = c->occ2_own.ensure((size_t)P * (size_t)(n_flows[i] > 1 ? n_flows[i] - 1 : 1))) != PSFM_OK) return st;
                 if ((st = psfm_solve_prepare(c, D[i], s)) != PSFM_OK) return st;
@@ -187,6 +194,9 @@ static psfm_status batch_run(psfm_ctx* const* ctxs, int n_seq, const float* cons
         // frame pairs -- ONE launch per chunk for all sequences (psfm_flow_check_x2v_batch_kernel) -- and the frame loop only waits
         // for the chunk it is about to read (what psfm_connect does for one sequence).  PSFM_BATCH_FC_CHUNK=0, or stacks the
         // 16-byte-load kernel cannot take: every stack up front on the launch stream.
+        // Option on: every stride-1 chunk is followed, on the side stream, by the kill-map launch of the same frames of all sequences
+        // (psfm_kill_map_batch_kernel reads the occlusion bytes of those frames only) and the chunk's event is recorded behind it, so
+        // that waiting for a chunk is waiting for its kill maps; up front, the kill maps follow their stack's flow_check.
         const int fc_env = getenv("PSFM_BATCH_FC_CHUNK") ? atoi(getenv("PSFM_BATCH_FC_CHUNK")) : -1;
         int fc_chunk = fc_env >= 0 ? fc_env : (optimize ? 6 : 8);
         for (int i = 0; i < B && fc_chunk > 0; ++i) {
@@ -215,18 +225,26 @@ static psfm_status batch_run(psfm_ctx* const* ctxs, int n_seq, const float* cons
                 if ((st = psfm_launch_flow_check(flows_f[i], flows_b[i], n_flows[i], h, w, thres, c->occ_own.as<uint8_t>(), nullptr, s)) != PSFM_OK) return st;
                 if (optimize && n_flows[i] > 1 &&
                     (st = psfm_launch_flow_check(flows_f2[i], flows_b2[i], n_flows[i] - 1, h, w, thres, c->occ2_own.as<uint8_t>(), nullptr, s)) != PSFM_OK) return st;
+                if (mb && (st = psfm_launch_motion_boundary(flows_f[i], c->occ_own.as<uint8_t>(), n_flows[i], h, w, c->mb_thres, c->kill.as<uint8_t>(), s)) != PSFM_OK)
+                    return st;
             }
         } else {
-            const size_t fbytes = sizeof(PsfmFcSeq) * (size_t)B * 2;
+            const size_t fc_bytes = sizeof(PsfmFcSeq) * (size_t)B * 2;
+            const size_t fbytes = fc_bytes + (mb ? sizeof(PsfmKmSeq) * (size_t)B : 0);      // (rows of 32 bytes, both)
             if ((st = batch_host_staging2(own, fbytes)) != PSFM_OK) return st;
             if ((st = own->batch_fc.ensure(fbytes)) != PSFM_OK) return st;
             PsfmFcSeq* hfc = (PsfmFcSeq*)own->host_batch2;
+            PsfmKmSeq* hkm = (PsfmKmSeq*)((char*)own->host_batch2 + fc_bytes);
             for (int i = 0; i < B; ++i) {
                 psfm_ctx* c = ctxs[i];
                 hfc[i].ff = flows_f[i]; hfc[i].fb = flows_b[i]; hfc[i].occ = c->occ_own.as<uint8_t>(); hfc[i].n_pairs = S[i].dropped ? 0 : n_flows[i]; hfc[i].pad = 0;
                 hfc[B + i].ff = optimize ? flows_f2[i] : nullptr; hfc[B + i].fb = optimize ? flows_b2[i] : nullptr;
                 hfc[B + i].occ = optimize ? c->occ2_own.as<uint8_t>() : nullptr;
                 hfc[B + i].n_pairs = (optimize && !S[i].dropped && n_flows[i] > 1) ? n_flows[i] - 1 : 0; hfc[B + i].pad = 0;
+                if (mb) {
+                    hkm[i].flows = flows_f[i]; hkm[i].occ = c->occ_own.as<uint8_t>(); hkm[i].out = c->kill.as<uint8_t>();
+                    hkm[i].n = hfc[i].n_pairs; hkm[i].thres = c->mb_thres;
+                }
             }
             PSFM_HIP(hipMemcpyAsync(own->batch_fc.p, hfc, fbytes, hipMemcpyHostToDevice, s));
             if (!own->side_stream) PSFM_HIP(hipStreamCreateWithFlags(&own->side_stream, hipStreamNonBlocking));
@@ -236,9 +254,12 @@ static psfm_status batch_run(psfm_ctx* const* ctxs, int n_seq, const float* cons
             PSFM_HIP(hipStreamWaitEvent(side, e_in, 0));
             fc_events.push_back(e_in);
             const PsfmFcSeq* dfc = own->batch_fc.as<PsfmFcSeq>();
+            const PsfmKmSeq* dkm = (const PsfmKmSeq*)((const char*)own->batch_fc.p + fc_bytes);
             for (int p0 = 0; p0 < n_max; p0 += fc_chunk) {
                 const int np = n_max - p0 < fc_chunk ? n_max - p0 : fc_chunk;
                 if ((st = psfm_launch_flow_check_batch(dfc, B, p0, np, h, w, thres, side)) != PSFM_OK) return st;
+                // (the stacks passed psfm_flow_check_batch_ok: P even, flows 16-byte aligned -- the four-pixels-per-lane form)
+                if (mb && (st = psfm_launch_kill_map_batch(dkm, B, p0, np, h, w, true, side)) != PSFM_OK) return st;
                 hipEvent_t e = own->prof.get();
                 PSFM_HIP(hipEventRecord(e, side));
                 fc_ready.push_back(e); fc_events.push_back(e);
@@ -269,11 +290,13 @@ static psfm_status batch_run(psfm_ctx* const* ctxs, int n_seq, const float* cons
         for (int i = 0; i < B; ++i) {
             psfm_ctx* c = ctxs[i];
             // (a sequence that has left the batch keeps a row -- blockIdx.y indexes the table -- with no frames to run)
-            psfm_batch_fill_seq(c, D[i], flows_f[i], c->occ_own.as<uint8_t>(), P, &htab[i]);
+            // (option on: the chain step's mask bytes are the sequence's kill maps; the caller's / the solve's occlusion maps stay 0/1)
+            const uint8_t* masks = mb ? c->kill.as<uint8_t>() : c->occ_own.as<uint8_t>();
+            psfm_batch_fill_seq(c, D[i], flows_f[i], masks, P, &htab[i]);
             if (S[i].dropped) htab[i].n_flows = 0;
             if (optimize) {
                 const float* f2 = n_flows[i] > 1 ? flows_f2[i] : flows_f[i];      // (a one-pair sequence has no stride-2 stack: never read)
-                if ((st = psfm_batch_fill_seq_opt(c, D[i], flows_f[i], c->occ_own.as<uint8_t>(), P, f2, c->occ2_own.as<uint8_t>(),
+                if ((st = psfm_batch_fill_seq_opt(c, D[i], flows_f[i], masks, P, f2, c->occ2_own.as<uint8_t>(),
                                                   htabo + row_opt * (size_t)i, s)) != PSFM_OK) return st;
                 // a run whose launches covered too few lanes has left the fused solve's tickets mid-count (blocks they were waiting
                 // for never existed): the run that repeats it starts them from zero
@@ -289,12 +312,12 @@ static psfm_status batch_run(psfm_ctx* const* ctxs, int n_seq, const float* cons
             // ---- track.py:31-47: one launch per frame index for the whole batch ----
             for (int f = 0; f < n_max; ++f) {
                 if ((st = fc_need(f, false)) != PSFM_OK) return st;
-                if ((st = psfm_launch_chain_step_batch(own, dtab, B, ratio, grid_lanes, f, false, s)) != PSFM_OK) return st;
+                if ((st = psfm_launch_chain_step_batch(own, dtab, B, ratio, grid_lanes, f, false, mb, s)) != PSFM_OK) return st;
             }
         } else {
             // ---- track_optimize.py:31-50: frame 0 is a plain chain step; from frame 1 on device-paced launches ----
             if ((st = fc_need(0, false)) != PSFM_OK) return st;
-            if ((st = psfm_launch_chain_step_batch(own, dtab, B, ratio, grid_lanes, 0, true, s)) != PSFM_OK) return st;
+            if ((st = psfm_launch_chain_step_batch(own, dtab, B, ratio, grid_lanes, 0, true, mb, s)) != PSFM_OK) return st;
             int launch_id = 0, idle_windows = 0;
             int v[PSFM_BATCH_MAX][4];
             for (int i = 0; i < B; ++i) {
@@ -328,7 +351,7 @@ static psfm_status batch_run(psfm_ctx* const* ctxs, int n_seq, const float* cons
                     if ((st = fc_need(f_hi, false)) != PSFM_OK) return st;
                     if ((st = fc_need(f_hi - 1, true)) != PSFM_OK) return st;
                 }
-                if ((st = psfm_launch_seq_batch(own, dtabo, B, ratio, grid_lanes, n_launch, launch_id, s)) != PSFM_OK) return st;
+                if ((st = psfm_launch_seq_batch(own, dtabo, B, ratio, grid_lanes, n_launch, launch_id, mb, s)) != PSFM_OK) return st;
                 launch_id += n_launch;
                 // ---- ONE checkpoint for all sequences ----
                 int lo[PSFM_BATCH_MAX];

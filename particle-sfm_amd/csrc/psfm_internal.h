@@ -156,7 +156,8 @@ struct psfm_ctx {
     PsfmBuf place_tab;    // birth masks per (frame, 64 grid points) as the loop leaves them | births of the virtual blocks as starts inside the frame | births per frame (psfm_place.h)
     int persist_max_blocks = -1;   // resident 256-thread blocks on this device (-1: not queried yet)
     int chain_mode = 0;            // 0 auto, 1 per-frame launches only, 2 persistent loop required
-    bool mb_enable = false;        // psfm_ctx_set_motion_boundary: tracks also die on motion boundaries (per-frame launches only)
+    bool mb_enable = false;        // psfm_ctx_set_motion_boundary: tracks also die on motion boundaries (per-frame launches; psfm_connect_batch
+                                   // when every context of the batch has it on)
     float mb_thres = 0.02f;
     PsfmBuf kill;                  // ... the kill maps of the sequence: (n_flows,H,W) u8, bit 0 occlusion, bit 1 motion boundary
     void* host_seg = nullptr;      // pinned staging for seg_info / seg_table
@@ -202,7 +203,8 @@ struct psfm_ctx {
     int solve_unroll = 6;   // iterations enqueued per frame without polling (adapted at checkpoints)
     PsfmBuf occ_own, occ2_own;           // occlusion maps of psfm_connect when the caller passes none
     PsfmBuf batch_tab, batch_ws, batch_fc;   // psfm_connect_batch (this context as the batch's owner): the table of sequences, packed
-                                         // checkpoints, the table of stacks for flow_check
+                                         // checkpoints, the table of stacks for flow_check (behind it, option on: the one for the kill maps)
+    PsfmBuf batch_km;                    // psfm_kill_map_batch: its table of stacks
     void* host_batch = nullptr;          // ... and their pinned staging
     size_t host_batch_bytes = 0;
     void* host_batch2 = nullptr;
@@ -332,14 +334,24 @@ bool psfm_flow_check_batch_ok(int h, int w, const void* ff, const void* fb, cons
 psfm_status psfm_launch_flow_check_batch(const PsfmFcSeq* tab_dev, int n_seq, int pair0, int n_pairs, int h, int w, float thres, hipStream_t s);
 void psfm_batch_fill_seq(psfm_ctx* c, const PsfmTrackDims& d, const float* flows, const uint8_t* occ, int64_t occ_pitch, PsfmBatchSeq* row);
 psfm_status psfm_launch_track_init_batch(const PsfmBatchSeq* tab_dev, int n_seq, int64_t cap_max, hipStream_t s);
+// mb: the rows' occlusion pointers are the sequences' kill maps and the step forms the motion-boundary verdict (psfm_motion_boundary.hip)
 psfm_status psfm_launch_chain_step_batch(psfm_ctx* owner, const PsfmBatchSeq* tab_dev, int n_seq, int ratio, int64_t cap_max, int frame,
-                                         bool optimize, hipStream_t s);
+                                         bool optimize, bool mb, hipStream_t s);
+psfm_status psfm_launch_chain_step_batch_mb(psfm_ctx* owner, const PsfmBatchSeq* tab_dev, int n_seq, int ratio, int64_t cap_max, int frame,
+                                            bool optimize, hipStream_t s);
+// the kill maps of a batch of stacks (psfm_motion_boundary.hip): one row per stack in device memory, frames [pair0, pair0 + n_pairs) of
+// every stack in ONE launch.  vec: P even and every flow stack 16-byte aligned (psfm_kill_map_batch_vec_ok); else one pixel per thread
+struct PsfmKmSeq { const float* flows; const uint8_t* occ; uint8_t* out; int n; float thres; };
+bool psfm_kill_map_batch_vec_ok(int h, int w, const void* flows);
+psfm_status psfm_launch_kill_map_batch(const PsfmKmSeq* tab_dev, int n_seq, int pair0, int n_pairs, int h, int w, bool vec, hipStream_t s);
 // track_optimize rows (psfm_solver_batch.hip: chain-step arguments + solver parameters of frame 1 + strides) and their launches
 size_t psfm_batch_seq_opt_bytes(void);
 psfm_status psfm_batch_fill_seq_opt(psfm_ctx* c, const PsfmTrackDims& d, const float* flows, const uint8_t* occ, int64_t occ_pitch,
                                     const float* flows_f2, const uint8_t* occ_s2, void* row_host, hipStream_t s);
 psfm_status psfm_launch_seq_batch(psfm_ctx* owner, const void* tab_dev, int n_seq, int ratio, int64_t cap_max, int n_launches, int launch_id0,
-                                  hipStream_t s);
+                                  bool mb, hipStream_t s);
+psfm_status psfm_launch_seq_batch_mb(psfm_ctx* owner, const void* tab_dev, int n_seq, int ratio, int64_t cap_max, int n_launches, int launch_id0,
+                                     hipStream_t s);      // (psfm_solver_batch_mb.hip: the chain step of the rows samples kill maps)
 psfm_status psfm_launch_flush_batch(const void* tab_dev, int n_seq, int64_t cap_max, hipStream_t s);
 psfm_status psfm_launch_batch_set_pc(const void* tab_dev, const int (*v)[4], int n_seq, hipStream_t s);
 size_t psfm_batch_pack_row_bytes(int win);

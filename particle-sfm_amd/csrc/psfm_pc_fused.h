@@ -27,45 +27,59 @@ __device__ __forceinline__ int pc_phys(int m, int e) { return m == e ? 0 : (m ==
 // kernel of a track-sharded run): tot[j * PC_NSUM + k].  first: the launch that started the solve (iteration 1 ..), else
 // a continuation behind `C.cur` accepted steps.  pc != NULL (device-paced sequence): the outcome also says what the NEXT
 // launch does -- the next frame, or more iterations of this solve when every one so far was accepted and none terminated.
+// The replay proper, on a control block C in memory of the function's choice (a macro: the two functions below differ in where C lives
+// and in nothing else, and the first must compile to what it always did).  Where a decision is not what was speculated, the launch chain
+// redoes the solve from the values it started from, which psfm_solve_frame_resume first moves back into buffer 0; a failed solve hands
+// the parameters back as they came in -- iterate 0 -- whatever it had accepted on the way (see the write-back).
+#define PC_FUSED_REPLAY_BODY \
+    const int base = first ? 0 : C.cur; \
+    const int k_first = first ? n_it : C.k_first; \
+    for (int j = 1; j <= n_it; ++j) { \
+        pc_control_step(C, tot + (j - 1) * PC_NSUM, first && j == 1, base + j); \
+        if (C.done) break; \
+        if (!(C.fresh_x && C.cur == base + j && C.dl_fixed == 0 && C.mu == 1e-8)) break; \
+    } \
+    C.k_first = k_first; \
+    C.launches += 1; \
+    *P.ctrl = C; \
+    const int e = k_first - 1; \
+    if (!C.done) { \
+        const bool all_accepted = C.fresh_x && C.cur == base + n_it && C.dl_fixed == 0 && C.mu == 1e-8; \
+        if (pc && all_accepted && C.cur + 1 <= PC_KMAX) { \
+            pc->pc_phase = 1; \
+            pc->pc_owner = launch_id + 1; \
+            return; \
+        } \
+        *P.sel = pc_phys(0, e); \
+        *P.stall = P.frame + 1; \
+        return; \
+    } \
+    *P.sel = pc_phys(C.failed ? 0 : C.cur, e); \
+    if (P.stats_dev) { \
+        psfm_solve_stats st; \
+        st.iterations = C.iteration; st.successful_steps = C.successful; \
+        st.termination = C.n_tracks == 0 ? -1 : C.termination; st.dogleg_nonGN = C.nonGN; \
+        st.initial_cost = C.initial_cost; st.final_cost = C.x_cost; \
+        if (C.failed) st.termination = PSFM_TERM_FAILURE; \
+        P.stats_dev[P.frame] = st; \
+    } \
+    if (pc) { pc->pc_frame = P.frame + 1; pc->pc_phase = 0; pc->pc_owner = launch_id + 1; }
 __device__ __forceinline__ void pc_fused_replay(const PcParams& P, const double* tot, int n_it, bool first, PsfmCounters* pc,
                                                 int launch_id, const PsfmSolveCtrl* c_in = nullptr)
 {
     PsfmSolveCtrl C = c_in ? *c_in : *P.ctrl;      // (c_in: the caller's copy of the control block, loaded with everything else it needs)
-    const int base = first ? 0 : C.cur;
-    const int k_first = first ? n_it : C.k_first;
-    for (int j = 1; j <= n_it; ++j) {
-        pc_control_step(C, tot + (j - 1) * PC_NSUM, first && j == 1, base + j);
-        if (C.done) break;
-        // iteration j + 1 was computed at iterate base + j with the Gauss-Newton step at min_mu: only valid behind an accepted step
-        if (!(C.fresh_x && C.cur == base + j && C.dl_fixed == 0 && C.mu == 1e-8)) break;
-    }
-    C.k_first = k_first;
-    C.launches += 1;
-    *P.ctrl = C;
-    const int e = k_first - 1;
-    if (!C.done) {
-        const bool all_accepted = C.fresh_x && C.cur == base + n_it && C.dl_fixed == 0 && C.mu == 1e-8;
-        if (pc && all_accepted && C.cur + 1 <= PC_KMAX) {     // device-paced: the next launch continues this solve
-            pc->pc_phase = 1;
-            pc->pc_owner = launch_id + 1;
-            return;
-        }
-        // not what was speculated: the launch chain redoes this solve from the values it started from,
-        *P.sel = pc_phys(0, e);   // which psfm_solve_frame_resume first moves back into buffer 0
-        *P.stall = P.frame + 1;
-        return;
-    }
-    // (a failed solve hands the parameters back as they came in -- iterate 0 -- whatever it had accepted on the way: see the write-back)
-    *P.sel = pc_phys(C.failed ? 0 : C.cur, e);
-    if (P.stats_dev) {
-        psfm_solve_stats st;
-        st.iterations = C.iteration; st.successful_steps = C.successful;
-        st.termination = C.n_tracks == 0 ? -1 : C.termination; st.dogleg_nonGN = C.nonGN;
-        st.initial_cost = C.initial_cost; st.final_cost = C.x_cost;
-        if (C.failed) st.termination = PSFM_TERM_FAILURE;
-        P.stats_dev[P.frame] = st;
-    }
-    if (pc) { pc->pc_frame = P.frame + 1; pc->pc_phase = 0; pc->pc_owner = launch_id + 1; }
+    PC_FUSED_REPLAY_BODY
+}
+
+// The same with ONE copy of the control block per block in LDS (232 bytes; thread 0 of the last block only).  The local copy above is
+// kept by the compiler as a per-thread array -- 2 KB of LDS per field, and what no longer fits the LDS of four blocks per CU in scratch --
+// which the batched sequence with the motion-boundary verdict (psfm_solver_batch_mb.hip) does without.
+__device__ __forceinline__ void pc_fused_replay_lds(const PcParams& P, const double* tot, int n_it, bool first, PsfmCounters* pc, int launch_id)
+{
+    __shared__ PsfmSolveCtrl s_ctrl;
+    PsfmSolveCtrl& C = s_ctrl;
+    C = *P.ctrl;
+    PC_FUSED_REPLAY_BODY
 }
 
 struct PcTrack {            // one track's solve state in registers
@@ -299,6 +313,7 @@ __device__ __forceinline__ const double* pc_grid_totals(const PcParams& P, PcWav
 // of them, whatever its lanes do: the tickets count them).  snap_next / n_lanes_live: the merged frame kernel leaves the
 // lane count for the next frame's launch.  pc / launch_id: device-paced sequence (see pc_fused_replay); there the K-th
 // candidate is stored too (a continuation launch starts from it).
+template <bool CTRL_LDS = false>      // (true: pc_fused_replay_lds)
 __device__ __forceinline__ void pc_fused_body(const PcParams& P, bool part, double2 p0, double2 p1, double2 p2, int n_active,
                                               int* snap_next, const int* n_lanes_live, PsfmCounters* pc, int launch_id, int lane0)
 {
@@ -336,12 +351,14 @@ __device__ __forceinline__ void pc_fused_body(const PcParams& P, bool part, doub
     }
     if (tid != 0) return;
     if (snap_next) *snap_next = *n_lanes_live;   // (every block is past its chain step: the count is final for this launch)
-    pc_fused_replay(P, tot, K, true, pc, launch_id);
+    if constexpr (CTRL_LDS) pc_fused_replay_lds(P, tot, K, true, pc, launch_id);
+    else pc_fused_replay(P, tot, K, true, pc, launch_id);
 }
 
 // Device-paced sequence: MORE iterations of the solve of P.frame, behind a launch whose K iterations were all accepted
 // without terminating it.  The track state is rebuilt from p0 and the start values (kept in buffer k_first - 1), the
 // iterate is read from where the previous launch left it, up to two more iterations are speculated the same way.
+template <bool CTRL_LDS = false>
 __device__ __forceinline__ void pc_more_body(const PcParams& P, int n_active, PsfmCounters* pc, int launch_id)
 {
     const PsfmSolveCtrl C0 = *P.ctrl;
@@ -375,7 +392,8 @@ __device__ __forceinline__ void pc_more_body(const PcParams& P, int n_active, Ps
     }
     const double* tot = pc_grid_totals(P, s_red, n_it, n_active);
     if (!tot || tid != 0) return;
-    pc_fused_replay(P, tot, n_it, false, pc, launch_id);
+    if constexpr (CTRL_LDS) pc_fused_replay_lds(P, tot, n_it, false, pc, launch_id);
+    else pc_fused_replay(P, tot, n_it, false, pc, launch_id);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -391,22 +409,43 @@ __device__ __forceinline__ void pc_more_body(const PcParams& P, int n_active, Ps
 // snapshot can be) sees pc_owner != launch_id and leaves.
 // ------------------------------------------------------------------------------------------------
 // what one block of a device-paced launch does for ITS sequence (psfm_seq_kernel: the launch's only sequence; psfm_seq_batch_kernel:
-// sequence blockIdx.y of the batch)
-template <int R>
+// sequence blockIdx.y of the batch).  MB: `a.occ` walks the sequence's kill maps and the chain step forms the motion-boundary verdict
+// (psfm_solver_batch_mb.hip); the solve reads the stride-2 occlusion maps only, which stay 0/1.
+template <int R, bool MB = false>
 __device__ __forceinline__ void psfm_seq_body(PsfmChainArgs a, PcParams P, const PsfmSeqStride st, int64_t occ2_stride, int n_flows, int launch_id)
 {
     PsfmCounters* ctr = a.ctr;
     if (ctr->stall || ctr->pc_owner != launch_id) return;
-    const int f = ctr->pc_frame, phase = ctr->pc_phase;
+    // (MB: the program counter is the same in every lane, and the form with the second verdict says so -- the frame's rebased pointers
+    // are then scalars, which is what keeps this form out of scratch at four waves per SIMD)
+    const int f = MB ? __builtin_amdgcn_readfirstlane(ctr->pc_frame) : ctr->pc_frame;
+    const int phase = MB ? __builtin_amdgcn_readfirstlane(ctr->pc_phase) : ctr->pc_phase;
     if (f >= n_flows) return;
     psfm_chain_args_rebase(a, st, f);
     pc_params_rebase(P, st, occ2_stride, f);
-    const int k = ctr->solve_K;
+    const int k = MB ? __builtin_amdgcn_readfirstlane(ctr->solve_K) : ctr->solve_K;
     P.K = k < 1 ? 1 : (k > PC_KMAX ? PC_KMAX : k);
-    const int n_active = min((max(ctr->n_lanes_snap[f & 1], a.Gband) + PC_BLOCK - 1) / PC_BLOCK, (int)gridDim.x);   // (as in psfm_frame_kernel)
+    // the blocks that take part in the solve's tickets (as in psfm_frame_kernel).  MB: read where it is used, behind the chain step --
+    // this launch writes the snapshot of the OTHER parity only -- so that it is not one more value alive across the step
+#define PSFM_SEQ_N_ACTIVE() min((max(ctr->n_lanes_snap[f & 1], a.Gband) + PC_BLOCK - 1) / PC_BLOCK, (int)gridDim.x)
+    if (MB) {
+        if (phase == 0) {
+            PsfmChainOut o;
+            if (!psfm_chain_step_body<R, true, true, true>(a, o)) return;
+            const int n_active = __builtin_amdgcn_readfirstlane(PSFM_SEQ_N_ACTIVE());      // (the same in every lane: a scalar)
+            pc_fused_body<true>(P, o.solve, o.p0, o.p1, o.p2, n_active, &ctr->n_lanes_snap[(f + 1) & 1], &ctr->n_lanes, ctr, launch_id, o.tile);
+        } else {
+            const int n_active = __builtin_amdgcn_readfirstlane(PSFM_SEQ_N_ACTIVE());      // (the same in every lane: a scalar)
+            if ((int)blockIdx.x >= n_active) return;
+            pc_more_body<true>(P, n_active, ctr, launch_id);
+        }
+        return;
+    }
+    const int n_active = PSFM_SEQ_N_ACTIVE();
+#undef PSFM_SEQ_N_ACTIVE
     if (phase == 0) {
         PsfmChainOut o;
-        if (!psfm_chain_step_body<R, true, true>(a, o)) return;
+        if (!psfm_chain_step_body<R, true, true, false>(a, o)) return;
         pc_fused_body(P, o.solve, o.p0, o.p1, o.p2, n_active, &ctr->n_lanes_snap[(f + 1) & 1], &ctr->n_lanes, ctr, launch_id, o.tile);
     } else {
         if ((int)blockIdx.x >= n_active) return;

@@ -91,8 +91,9 @@ psfm_status psfm_batch_fill_seq_opt(psfm_ctx* c, const PsfmTrackDims& d, const f
 }
 
 psfm_status psfm_launch_seq_batch(psfm_ctx* owner, const void* tab_dev, int n_seq, int ratio, int64_t cap_max, int n_launches, int launch_id0,
-                                  hipStream_t s)
+                                  bool mb, hipStream_t s)
 {
+    if (mb) return psfm_launch_seq_batch_mb(owner, tab_dev, n_seq, ratio, cap_max, n_launches, launch_id0, s);      // (kernels of psfm_solver_batch_mb.hip)
     const unsigned gx = (unsigned)(((cap_max + PC_BLOCK - 1) / PC_BLOCK + 7) / 8 * 8);
     const dim3 grid(gx, (unsigned)n_seq), block(PC_BLOCK);
     const PsfmBatchSeqOpt* tab = (const PsfmBatchSeqOpt*)tab_dev;

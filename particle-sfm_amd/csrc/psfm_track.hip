@@ -516,8 +516,9 @@ psfm_status psfm_launch_track_init_batch(const PsfmBatchSeq* tab_dev, int n_seq,
 }
 
 psfm_status psfm_launch_chain_step_batch(psfm_ctx* owner, const PsfmBatchSeq* tab_dev, int n_seq, int ratio, int64_t cap_max, int frame,
-                                         bool optimize, hipStream_t s)
+                                         bool optimize, bool mb, hipStream_t s)
 {
+    if (mb) return psfm_launch_chain_step_batch_mb(owner, tab_dev, n_seq, ratio, cap_max, frame, optimize, s);      // (kernels of psfm_motion_boundary.hip)
     hipEvent_t e0 = nullptr, e1 = nullptr;
     owner->prof.kernel_span(PSFM_PROF_CHAIN, &e0, &e1);
     const unsigned gx = (unsigned)(((cap_max + PSFM_CHAIN_TILE - 1) / PSFM_CHAIN_TILE + 7) / 8 * 8);

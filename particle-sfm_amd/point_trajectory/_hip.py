@@ -35,7 +35,7 @@ EXPORTS = [
     "psfm_database_compact_again",
     "psfm_sparse_depth", "psfm_sparse_depth_sort_ids", "psfm_ctx_set_sparse_depth", "psfm_ctx_get_sparse_depth_budget",
     "psfm_sparse_depth_last_ms", "psfm_colmap_points3d_count", "psfm_colmap_points3d_scan",
-    "psfm_ctx_set_motion_boundary", "psfm_motion_boundary", "psfm_kill_map",
+    "psfm_ctx_set_motion_boundary", "psfm_motion_boundary", "psfm_kill_map", "psfm_kill_map_batch",
     "psfm_depth_display", "psfm_ctx_set_depth_display", "psfm_depth_display_last_ms", "psfm_depth_display_chunk",
     "psfm_track_queries", "psfm_track_queries_optimize",
     "psfm_result_filter_batch", "psfm_traj_to_matches_batch", "psfm_labels_to_matches_batch", "psfm_matches_batch_census", "psfm_labels_sizes",
@@ -114,6 +114,8 @@ def lib():
     L.psfm_ctx_set_motion_boundary.argtypes = [vp, i32, f32]
     L.psfm_motion_boundary.argtypes = [vp, vp, i32, i32, i32, f32, vp, vp]
     L.psfm_kill_map.argtypes = [vp, vp, vp, i32, i32, i32, f32, vp, vp]
+    L.psfm_kill_map_batch.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(i32), i32, i32, i32, ctypes.POINTER(f32), i32, i32,
+                                      ctypes.POINTER(vp), vp]
     L.psfm_solver_counters.argtypes = [vp, ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(ctypes.c_int32)]
     L.psfm_ctx_set_resident_budget.argtypes = [vp, i32]
     L.psfm_resident_capacity.argtypes = [vp, ctypes.POINTER(ctypes.c_int32)]
@@ -230,7 +232,8 @@ class Context:
 
     def set_motion_boundary(self, enable, thres=0.02):
         """Tracks also die on motion boundaries (the reference's commented kill rule, trajectory.py:60): psfm_track / psfm_connect
-        then run one launch per frame; psfm_connect_batch and psfm_shard_begin refuse the context.  Default off."""
+        then run one launch per frame; psfm_connect_batch takes the option on all of its contexts or on none; psfm_shard_begin refuses
+        the context.  Default off."""
         check(lib().psfm_ctx_set_motion_boundary(self._h, int(bool(enable)), float(thres)))
 
     def set_solver(self, mode, k=0):

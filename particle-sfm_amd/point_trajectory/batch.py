@@ -12,6 +12,7 @@ Sequences are the unit that shards exactly:
     (3.5-5x the sequences per second of one psfm_connect each on a DAVIS-sized stack, 2.3x with path consistency on a
     Sintel-sized one; profiles/r05).  Host threads still overlap the .flo ingest / track.npy writing of one batch with the
     compute of another.
+    With motion_boundary=True the batch carries the second kill rule (every context of the batch gets the option).
 """
 import threading
 
@@ -23,17 +24,22 @@ BATCH_MAX = 64                 # PSFM_BATCH_MAX of csrc/psfm_batch.hip: sequence
 BATCH_BYTES = 48 << 30         # flow stacks of one group resident in HBM before its compute starts (of 288 GB)
 
 
-def _connect_batch_to_disk(flow_dirs, traj_dirs, sample_ratio, flow_check_thres, traj_min_len, skip_path_consistency, skip_exists, layout):
+def _connect_batch_to_disk(flow_dirs, traj_dirs, sample_ratio, flow_check_thres, traj_min_len, skip_path_consistency, skip_exists, layout,
+                           motion_boundary=False, mb_thres=0.02, mb_engine=None):
     """main_connect_point_trajectories.py:27-62 for a group of sequences through psfm_connect_batch: ingest all, ONE batched
-    compute call per frame size, then filter + save each from its own context."""
+    compute call per frame size, then filter + save each from its own context.  motion_boundary / mb_thres / mb_engine: as in run_connect_batch
+    (the PSFM_MOTION_BOUNDARY switch of the one-sequence entry point holds here too)."""
     import os
     from .utils import load_flows_device
     from .trajectory import run_connect_batch, result_to_trajectory_set, save_track_npy
     import glob
     from .main_connect_point_trajectories import main_connect_point_trajectories
 
+    motion_boundary = bool(motion_boundary) or os.environ.get("PSFM_MOTION_BOUNDARY", "0") == "1"
+
     def flush(group):
-        ctxs, infos = run_connect_batch([sq for _, sq in group], flow_check_thres, sample_ratio)
+        ctxs, infos = run_connect_batch([sq for _, sq in group], flow_check_thres, sample_ratio, motion_boundary=motion_boundary, mb_thres=mb_thres,
+                                        mb_engine=mb_engine)
         for (td, _), ctx, info in zip(group, ctxs, infos):
             ts = result_to_trajectory_set(ctx, info, traj_min_len, reuse_pinned=True)
             save_track_npy(os.path.join(td, "track.npy"), ts, layout=layout)
@@ -49,7 +55,8 @@ def _connect_batch_to_disk(flow_dirs, traj_dirs, sample_ratio, flow_check_thres,
             continue
         if not glob.glob(os.path.join(fd, "flow_f", "*.flo")):
             main_connect_point_trajectories(fd, td, sample_ratio=sample_ratio, flow_check_thres=flow_check_thres, traj_min_len=traj_min_len,
-                                            skip_path_consistency=skip_path_consistency, skip_exists=skip_exists, layout=layout)
+                                            skip_path_consistency=skip_path_consistency, skip_exists=skip_exists, layout=layout,
+                                            motion_boundary=motion_boundary, mb_thres=mb_thres)
             continue
         f, b = load_flows_device(os.path.join(fd, "flow_f")), load_flows_device(os.path.join(fd, "flow_b"))
         f2 = b2 = None
@@ -67,11 +74,14 @@ def _connect_batch_to_disk(flow_dirs, traj_dirs, sample_ratio, flow_check_thres,
 
 
 def connect_sequences(flow_dirs, traj_dirs, sample_ratio=2, flow_check_thres=1.0, traj_min_len=3,
-                      skip_path_consistency=False, skip_exists=False, concurrency=2, rank=None, world=None, layout="csr", batch=1):
+                      skip_path_consistency=False, skip_exists=False, concurrency=2, rank=None, world=None, layout="csr", batch=1,
+                      motion_boundary=False, mb_thres=0.02, mb_engine=None):
     """main_connect_point_trajectories for a list of sequences; returns the indices this rank processed.
     layout: pickle state of the track.npy files -- "csr" (default here: the batch driver is this package's own entry
     point and its files are read back through this package) or "reference" (files for an unmodified checkout).
-    batch > 1: every worker takes up to `batch` sequences at a time through psfm_connect_batch (small frames: see above)."""
+    batch > 1: every worker takes up to `batch` sequences at a time through psfm_connect_batch (small frames: see above).
+    motion_boundary / mb_thres: tracks also die on motion boundaries (run_connect / run_connect_batch), on either route; mb_engine: how
+    a batch runs with the option (run_connect_batch; None: its default)."""
     import torch
     import psfm_dist
     if rank is None or world is None:
@@ -114,12 +124,13 @@ def connect_sequences(flow_dirs, traj_dirs, sample_ratio=2, flow_check_thres=1.0
                             k = todo.pop(0)
                     if batch > 1:
                         _connect_batch_to_disk([flow_dirs[k] for k in ks], [traj_dirs[k] for k in ks], sample_ratio, flow_check_thres,
-                                               traj_min_len, skip_path_consistency, skip_exists, layout)
+                                               traj_min_len, skip_path_consistency, skip_exists, layout, motion_boundary=motion_boundary,
+                                               mb_thres=mb_thres, mb_engine=mb_engine)
                         continue
                     main_connect_point_trajectories(flow_dirs[k], traj_dirs[k], sample_ratio=sample_ratio,
                                                     flow_check_thres=flow_check_thres, traj_min_len=traj_min_len,
                                                     skip_path_consistency=skip_path_consistency, skip_exists=skip_exists,
-                                                    layout=layout)
+                                                    layout=layout, motion_boundary=motion_boundary, mb_thres=mb_thres)
                 stream.synchronize()
         except Exception as e:   # surface the first failure in the caller
             with lock:

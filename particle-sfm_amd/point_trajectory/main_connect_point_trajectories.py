@@ -11,13 +11,15 @@ from .trajectory import run_connect, result_to_trajectory_set, save_track_npy
 
 
 def main_connect_point_trajectories(flow_dir, traj_dir, sample_ratio=2, flow_check_thres=1.0, traj_min_len=3,
-                                    skip_path_consistency=False, skip_exists=False, layout=None, timings=None, motion_boundary=False):
+                                    skip_path_consistency=False, skip_exists=False, layout=None, timings=None, motion_boundary=False,
+                                    mb_thres=0.02):
     """Reference signature (:27) plus `layout`: the pickle state of track.npy -- "reference" (default; the file an
     unmodified particle-sfm checkout, pybind module included, reads) or "csr" (this package's compact arrays;
     PSFM_TRACK_LAYOUT=csr selects it for callers that cannot pass the argument) -- and `timings`: a dict that receives the
     seconds of the stage's phases (ingest / compute / filter_d2h / write) -- and `motion_boundary`: tracks also die
     on motion boundaries, the kill rule the reference keeps commented out for in-the-wild video (trajectory.py:58-60;
-    PSFM_MOTION_BOUNDARY=1 selects it for callers that cannot pass the argument, e.g. through run_with_psfm.py --motion_boundary)."""
+    PSFM_MOTION_BOUNDARY=1 selects it for callers that cannot pass the argument, e.g. through run_with_psfm.py --motion_boundary), with
+    `mb_thres` its threshold (the reference's 0.02)."""
     import time
     import torch
     t0 = time.perf_counter()
@@ -43,7 +45,7 @@ def main_connect_point_trajectories(flow_dir, traj_dir, sample_ratio=2, flow_che
     # one call, the occlusion maps stream into the frame loop from a side stream
     motion_boundary = bool(motion_boundary) or os.environ.get("PSFM_MOTION_BOUNDARY", "0") == "1"
     info = run_connect(flows_f, flows_b, flows_f2, flows_b2, flow_check_thres, sample_ratio, return_device=True,
-                       motion_boundary=motion_boundary)
+                       motion_boundary=motion_boundary, mb_thres=mb_thres)
     if timings is not None:
         torch.cuda.synchronize()
     t2 = time.perf_counter()

@@ -58,6 +58,37 @@ def motion_boundary(flow, thres=0.02):
         return motion > thres * np.linalg.norm(f, ord=2, axis=-1)
 
 
+def kill_map_batch(flows, occ, thres=0.02, pair0=0, n_pairs=None, out=None, ctx=None):
+    """psfm_kill_map_batch: the kill maps (bit 0 occlusion, bit 1 motion boundary) of up to 64 same-shape stacks in ONE launch,
+    frames [pair0, pair0 + n_pairs) of every stack (default: to the end of the longest).
+    flows: list of (n_i,H,W,2) float32 device tensors; occ: list of (n_i,H,W) uint8 device tensors; thres: one value or one per
+    stack; out: list of (n_i,H,W) uint8 device tensors to write into (default: new ones, zero outside the range).  Returns `out`.
+    Only the occlusion bytes of the frames of the range are read and only their kill bytes written."""
+    import torch
+    n_seq = len(flows)
+    if ctx is None:
+        ctx = _hip.context()
+    th = [float(thres)] * n_seq if np.isscalar(thres) else [float(t) for t in thres]
+    if len(occ) != n_seq or len(th) != n_seq or (out is not None and len(out) != n_seq):
+        raise ValueError("kill_map_batch: %d stacks need as many occlusion stacks, thresholds and outputs" % n_seq)
+    H, W = (int(flows[0].shape[1]), int(flows[0].shape[2])) if n_seq else (0, 0)
+    for i in range(n_seq):
+        if (not flows[i].is_cuda or flows[i].dtype != torch.float32 or not flows[i].is_contiguous() or tuple(flows[i].shape[1:]) != (H, W, 2)
+                or occ[i].dtype != torch.uint8 or not occ[i].is_contiguous() or tuple(occ[i].shape) != tuple(flows[i].shape[:3])):
+            raise ValueError("kill_map_batch: stack %d is not a contiguous (n,%d,%d,2) float32 / (n,%d,%d) uint8 pair on the device" % (i, H, W, H, W))
+    if out is None:
+        out = [torch.zeros_like(o) for o in occ]
+    n = [int(f.shape[0]) for f in flows]
+    if n_pairs is None:
+        n_pairs = max(max(n, default=0) - int(pair0), 0)
+    vp = ctypes.c_void_p
+    _hip.check(_hip.lib().psfm_kill_map_batch(
+        ctx.handle, (vp * n_seq)(*[f.data_ptr() for f in flows]), (vp * n_seq)(*[o.data_ptr() for o in occ]), (ctypes.c_int * n_seq)(*n), n_seq,
+        H, W, (ctypes.c_float * n_seq)(*th), int(pair0), int(n_pairs), (vp * n_seq)(*[o.data_ptr() for o in out]),
+        _hip.current_stream_ptr(ctx.device)))
+    return out
+
+
 class _MotionBoundary:
     """Sets psfm_ctx_set_motion_boundary on a context for the duration of one call (the option is per context, off by default)."""
 
@@ -330,23 +361,38 @@ def run_connect(flows_f, flows_b, flows_f2, flows_b2, thres, sample_ratio, retur
     return _result_to_host(ctx, info)
 
 
-def run_connect_batch(seqs, thres, sample_ratio, motion_boundary=False, mb_thres=0.02):
+# How run_connect_batch(..., motion_boundary=True) runs when the caller does not say: "batch" (psfm_connect_batch with the option on in
+# every context) or "loop" (one psfm_connect per sequence).  Measured (scripts/micro/motion_boundary_batch.py, profiles/EXPERIMENTS.md
+# section 28): 5.1-5.4x on DAVIS-sized batches in track mode, 3.0x on Sintel-sized ones with path consistency, same results.
+MB_ENGINE_DEFAULT = "batch"
+
+
+def run_connect_batch(seqs, thres, sample_ratio, motion_boundary=False, mb_thres=0.02, mb_engine=None):
     """psfm_connect_batch: flow_check + track / track_optimize for a BATCH of same-shape sequences (the directory of sequences the
     reference's driver walks, run_particlesfm.py:168-176) with every frame launch covering the whole batch.
     seqs: list of (flows_f, flows_b, flows_f2 | None, flows_b2 | None) device tensors (n_i,H,W,2) -- all with stride-2 stacks or
     none.  Returns (contexts, infos): context i holds sequence i's result (`_result_to_host(ctx, info)`,
     `result_to_trajectory_set(ctx, info)`) until the calling thread's next batch.
-    motion_boundary: the batched launches do not form that verdict (psfm_connect_batch refuses such a context): the sequences then
-    go through run_connect one after the other, each on its own context."""
+    motion_boundary: tracks also die on motion boundaries of threshold mb_thres (one value, or one per sequence).  mb_engine "batch":
+    the option is set on every batch context for the duration of the call and the batched launches form the verdict; "loop": the
+    sequences go through run_connect one after the other, each on its own context; None: MB_ENGINE_DEFAULT.  Same results."""
     import torch
     n_seq = len(seqs)
     if n_seq < 1:
         return [], []
+    mb_list = None
     if motion_boundary:
-        ctxs = _hip.batch_contexts(n_seq)
-        infos = [run_connect(a, b, a2, b2_, thres, sample_ratio, return_device=True, motion_boundary=True, mb_thres=mb_thres, ctx=c)
-                 for c, (a, b, a2, b2_) in zip(ctxs, seqs)]
-        return ctxs, infos
+        mb_list = [float(mb_thres)] * n_seq if np.isscalar(mb_thres) else [float(t) for t in mb_thres]
+        if len(mb_list) != n_seq:
+            raise ValueError("connect_batch: %d thresholds for %d sequences" % (len(mb_list), n_seq))
+        engine = MB_ENGINE_DEFAULT if mb_engine is None else mb_engine
+        if engine not in ("batch", "loop"):
+            raise ValueError("connect_batch: mb_engine must be 'batch', 'loop' or None")
+        if engine == "loop":
+            ctxs = _hip.batch_contexts(n_seq)
+            infos = [run_connect(a, b, a2, b2_, thres, sample_ratio, return_device=True, motion_boundary=True, mb_thres=t, ctx=c)
+                     for c, t, (a, b, a2, b2_) in zip(ctxs, mb_list, seqs)]
+            return ctxs, infos
     H, W = int(seqs[0][0].shape[1]), int(seqs[0][0].shape[2])
     opt = seqs[0][2] is not None
     keep = []           # (tensors created here must outlive the call)
@@ -373,15 +419,23 @@ def run_connect_batch(seqs, thres, sample_ratio, motion_boundary=False, mb_thres
     infos = (_hip.TrackInfo * n_seq)()
     cap_key = ("batch", H, W, int(sample_ratio), opt)
     lane_f, traj_f = _capacity_of(ctxs[0], cap_key)
-    for attempt in range(6):
-        for c in ctxs:
-            c.set_capacity(lane_f, traj_f)
-        ctxs[0]._capacity[cap_key] = (lane_f, traj_f)
-        st = _hip.lib().psfm_connect_batch(handles, n_seq, ff, fb, f2 if opt else None, b2 if opt else None, nf, H, W, float(thres),
-                                           int(sample_ratio), infos, _hip.current_stream_ptr(ctxs[0].device))
-        if st != _hip.PSFM_ERR_CAPACITY:
-            break
-        lane_f, traj_f = lane_f * 2.0, traj_f * 4.0      # tables too small for one of the sequences: grow all and rerun
+    try:
+        if mb_list is not None:
+            for c, t in zip(ctxs, mb_list):
+                c.set_motion_boundary(True, t)
+        for attempt in range(6):
+            for c in ctxs:
+                c.set_capacity(lane_f, traj_f)
+            ctxs[0]._capacity[cap_key] = (lane_f, traj_f)
+            st = _hip.lib().psfm_connect_batch(handles, n_seq, ff, fb, f2 if opt else None, b2 if opt else None, nf, H, W, float(thres),
+                                               int(sample_ratio), infos, _hip.current_stream_ptr(ctxs[0].device))
+            if st != _hip.PSFM_ERR_CAPACITY:
+                break
+            lane_f, traj_f = lane_f * 2.0, traj_f * 4.0      # tables too small for one of the sequences: grow all and rerun
+    finally:
+        if mb_list is not None:      # (the option is per context and the thread's batch contexts are reused: off again, whatever happened)
+            for c in ctxs:
+                c.set_motion_boundary(False)
     _hip.check(st)
     return ctxs, [infos[i] for i in range(n_seq)]
 
