@@ -166,10 +166,11 @@ __host__ __device__ __forceinline__ int psfm_mtb_key_seq(unsigned long long key,
 __host__ __device__ __forceinline__ unsigned long long psfm_mtb_key_mask(int local_bits) { return (1ull << local_bits) - 1ull; }
 
 // Bits of the composed key over keys < local_range in n_seq sequences; 0: it does not fit 64 bits (the shift of psfm_mtb_key needs
-// local_bits < 64 as well, so a 64-bit local key is refused even for one sequence).
+// local_bits < 64 as well, so a 64-bit local key is refused even for one sequence).  One sequence spends no bit on the sequence:
+// its composed key is the local key, and the sorts run over the bits the single calls sort (psfm_matches.hip).
 inline int psfm_mtb_key_bits(int n_seq, unsigned long long local_range, int* local_bits)
 {
-    const int lb = psfm_mtb_bits(local_range), sb = psfm_mtb_bits((unsigned long long)n_seq);
+    const int lb = psfm_mtb_bits(local_range), sb = n_seq > 1 ? psfm_mtb_bits((unsigned long long)n_seq) : 0;
     *local_bits = lb;
     if (lb >= 64 || (local_range > 1 && (1ull << lb) < local_range)) return 0;
     return lb + sb <= 64 ? lb + sb : 0;

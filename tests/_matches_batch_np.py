@@ -3,7 +3,8 @@ sort ONCE with the sequence above the key -- (b, frame) and (b, src * n_img[b] +
 cumulative sums read at the sequence bases, then split and make everything sequence-local.  tests/test_matches_batch_host.py holds
 it against psfm_sfm.matches_from_flow.match_tables_host per sequence (which tests/test_consumers_golden.py pins to the reference)
 and against the host build of psfm_matches_batch.h; tests/test_gpu_matches_batch.py holds the device against both.  Also: the
-lookup of a block on the flattened grid, the bases, the key codec, the grouping rule, and the hand-shaped batch of the tests."""
+lookup of a block on the flattened grid, the bases, the key codec, the grouping rule, the hand-shaped batch of the tests, and the
+sets that take the single entry points to the edges of a block and of the key widths."""
 import numpy as np
 
 MAX_SEQ, BLOCK, INT32_MAX = 64, 256, 2 ** 31 - 1
@@ -18,8 +19,8 @@ def bits_np(v):
 
 
 def key_bits_np(n_seq, local_range):
-    """(bits of the composed key or 0 when it does not fit 64, bits of the local key)"""
-    lb, sb = bits_np(local_range), bits_np(n_seq)
+    """(bits of the composed key or 0 when it does not fit 64, bits of the local key); one sequence spends no bit on the sequence"""
+    lb, sb = bits_np(local_range), (bits_np(n_seq) if n_seq > 1 else 0)
     if lb >= 64 or (1 << lb) < local_range:
         return 0, lb
     return (lb + sb if lb + sb <= 64 else 0), lb
@@ -178,6 +179,66 @@ def orders():
     """The list as it is, with the empty set moved to the front, and to the back."""
     base = hand_shaped_batch()
     return {"as_listed": base, "empty_first": [base[1]] + base[:1] + base[2:], "empty_last": base[:1] + base[2:] + [base[1]]}
+
+
+# ---- the sets for the single entry points at their edges --------------------------------------------------------------------------
+
+EDGE_LENGTHS = (1, 2, 20, 21, 40, 41)          # no match; a pair; both sides of sample_k = 20; stride 2 with and without j // 2 >= 20
+EDGE_POINTS = (1, 255, 256, 257, 513)          # the edges of a 256-thread block, and a third block
+EDGE_N_IMG = (1, 2, 255, 256, 257)             # frame key 8 -> 9 bits, pair key 16 -> 17 bits
+
+
+def edge_lengths(n_points):
+    """Trajectory lengths that add up to n_points: each of EDGE_LENGTHS once where it fits, then again, largest first."""
+    out, left = [], n_points
+    for n in EDGE_LENGTHS:
+        if n <= left:
+            out.append(n)
+            left -= n
+    while left:
+        for n in reversed(EDGE_LENGTHS):
+            if n <= left:
+                out.append(n)
+                left -= n
+    return out
+
+
+def edge_set(n_points, seed, n_img=64, dynamic=0.3):
+    """A labelled set of n_points points in edge_lengths trajectories; a trajectory's frames are distinct images drawn from all
+    n_img in random order: not ascending, with gaps."""
+    rng = np.random.default_rng(seed)
+    lengths = edge_lengths(n_points)
+    off = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+    frames = np.concatenate([rng.permutation(n_img)[:n] for n in lengths]).astype(np.int64)
+    xy = rng.uniform(0, 500, size=(n_points, 2))
+    return off, frames, xy, rng.random(n_points) < dynamic, n_img
+
+
+def n_img_set(n_img, seed):
+    """A set without dynamic points on n_img images: trajectories of 2, 20, 21, 41, 1 and 2 points where n_img has room for their
+    distinct frames (five one-point trajectories on one image); the first one is (last image, image 0)."""
+    rng = np.random.default_rng(seed)
+    lengths = [n for n in (2, 20, 21, 41, 1, 2) if n <= n_img] if n_img > 1 else [1] * 5
+    off = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+    frames = [rng.permutation(n_img)[:n] for n in lengths]
+    if n_img > 1:
+        frames[0] = np.array([n_img - 1, 0])
+    frames = np.concatenate(frames).astype(np.int64)
+    return off, frames, rng.uniform(0, 500, size=(len(frames), 2)), np.zeros(len(frames), bool), n_img
+
+
+def n_matches_np(kept_lengths, sample_k=20):
+    """matches of trajectories with these numbers of kept points (matches_from_flow.py:83-101), counted point by point"""
+    total = 0
+    for n in kept_lengths:
+        stride = max(n // sample_k, 1)
+        total += n * (n - 1) if n <= sample_k else sum(sample_k - (1 if j % stride == 0 and j // stride < sample_k else 0) for j in range(n))
+    return total
+
+
+EDGE_SETS = {n: edge_set(n, 40 + i) for i, n in enumerate(EDGE_POINTS)}
+ALL_DYNAMIC_SET = edge_set(257, 50, dynamic=2.0)
+N_IMG_SETS = {n: n_img_set(n, 60 + i) for i, n in enumerate(EDGE_N_IMG)}
 
 
 def random_sets(n, seed, max_points=300):

@@ -404,3 +404,83 @@ def test_grouped_python_functions(pt, connected, tmp_path):
         for name in names[b]:
             assert np.array_equal(out[b][name].keypoints, one[name].keypoints) and list(out[b][name].match_pairs) == list(one[name].match_pairs)
             assert all(np.array_equal(out[b][name].match_pairs[k], one[name].match_pairs[k]) for k in one[name].match_pairs)
+
+
+# ---- 8. the single entry points at their edges (psfm_labels_to_matches through ctypes, bit-compared with the model) -------------------
+# tests/test_matches_batch_host.py::test_the_edge_sets_are_what_they_say holds every property claimed of these sets
+
+def labels_single(pt, ctx, n_img, remove_dynamic=True):
+    a, b, c = ctypes.c_int64(-1), ctypes.c_int64(-1), ctypes.c_int64(-1)
+    pt.hip.check(pt.hip.lib().psfm_labels_to_matches(ctx.handle, int(n_img), pt.mff.SAMPLE_K, 1 if remove_dynamic else 0, ctypes.byref(a),
+                                                     ctypes.byref(b), ctypes.byref(c), pt.hip.current_stream_ptr(ctx.device)))
+    return int(a.value), int(b.value), int(c.value)
+
+
+def single_equals_model(pt, ctx, models, seq, remove_dynamic=True, what=""):
+    want = models(seq, remove_dynamic)
+    sizes = labels_single(pt, ctx, seq[4], remove_dynamic)
+    assert sizes == (len(want[1]), len(want[5]), len(want[2])), what
+    assert_tables_bit_equal(copy_tables(pt, ctx, seq[4], sizes), want, what)
+    return sizes
+
+
+@pytest.mark.parametrize("remove_dynamic", [True, False])
+@pytest.mark.parametrize("n_points", mb.EDGE_POINTS)
+def test_single_call_at_the_edges_of_a_block(pt, models, n_points, remove_dynamic):
+    """1, 255, 256, 257 and 513 points in trajectories of 1, 2, 20, 21, 40 and 41 points, frames not ascending and with gaps"""
+    seq = mb.EDGE_SETS[n_points]
+    ctx = pt.hip.batch_contexts(1)[0]
+    labels_set(pt, ctx, *seq[:4])
+    sizes = single_equals_model(pt, ctx, models, seq, remove_dynamic)
+    assert (sizes[1] > 0) == (n_points > 1) and len(seq[1]) == n_points
+
+
+def test_single_call_with_every_point_dynamic(pt, models):
+    seq = mb.ALL_DYNAMIC_SET
+    ctx = pt.hip.batch_contexts(1)[0]
+    labels_set(pt, ctx, *seq[:4])
+    room = single_equals_model(pt, ctx, models, seq, False)             # every point kept
+    assert room[0] == 257 and room[1] > 1000
+    assert labels_single(pt, ctx, seq[4], True) == (0, 0, 0)            # every point dropped: the earlier tables are gone
+    copy_expecting_empty(pt, ctx, seq[4], room)
+    assert_tables_bit_equal(copy_tables(pt, ctx, seq[4], (0, 0, 0)), models(seq, True))
+
+
+@pytest.mark.parametrize("n_img", mb.EDGE_N_IMG)
+def test_single_call_at_the_edges_of_the_key_widths(pt, models, n_img):
+    """n_img 1, 2, 255, 256, 257: the frame key grows from 8 to 9 bits, the pair key from 16 to 17; a point in the last image"""
+    seq = mb.N_IMG_SETS[n_img]
+    ctx = pt.hip.batch_contexts(1)[0]
+    labels_set(pt, ctx, *seq[:4])
+    sizes = single_equals_model(pt, ctx, models, seq)
+    assert (sizes[1] > 0) == (n_img > 1) and int(seq[1].max()) == n_img - 1
+    # the same set as a batch of one and as the second sequence of a batch of two: the composed key with 0 and with 1 sequence bit
+    ctxs = pt.hip.batch_contexts(2)
+    assert labels_batch(pt, ctxs[:1], [n_img]) == [sizes]
+    assert_tables_bit_equal(copy_tables(pt, ctxs[0], n_img, sizes), models(seq), "batch of one")
+    first = mb.N_IMG_SETS[2]
+    load_sets(pt, ctxs, [first, seq])
+    both = labels_batch(pt, ctxs, [2, n_img])
+    assert both[1] == sizes
+    assert_tables_bit_equal(copy_tables(pt, ctxs[1], n_img, sizes), models(seq), "second of two")
+    assert_tables_bit_equal(copy_tables(pt, ctxs[0], 2, both[0]), models(first), "first of two")
+
+
+def test_single_calls_and_batch_calls_in_any_order_on_the_same_contexts(pt, models):
+    """a single call on the context that owned a batch call's intermediates, one on a context that did not, and a batch call behind
+    them with the contexts the other way round"""
+    seqs = mb.hand_shaped_batch()
+    a, b = seqs[0], seqs[6]
+    ctxs = pt.hip.batch_contexts(2)
+    load_sets(pt, ctxs, [a, b])
+    sizes = labels_batch(pt, ctxs, [a[4], b[4]])
+    assert single_equals_model(pt, ctxs[0], models, a, what="ctxs[0] after the batch call") == sizes[0]
+    assert single_equals_model(pt, ctxs[1], models, b, what="ctxs[1] after the batch call") == sizes[1]
+    for c, s, n in ((ctxs[0], a, sizes[0]), (ctxs[1], b, sizes[1])):     # neither call touched the other context
+        assert_tables_bit_equal(copy_tables(pt, c, s[4], n), models(s))
+    load_sets(pt, ctxs, [b, a])                                          # the larger set moves to the other context
+    assert labels_batch(pt, [ctxs[1], ctxs[0]], [a[4], b[4]]) == sizes
+    assert_tables_bit_equal(copy_tables(pt, ctxs[1], a[4], sizes[0]), models(a), "ctxs[1] as the owner")
+    assert_tables_bit_equal(copy_tables(pt, ctxs[0], b[4], sizes[1]), models(b), "ctxs[0] as the second")
+    assert single_equals_model(pt, ctxs[0], models, b, what="ctxs[0] after the second batch call") == sizes[1]
+    assert sizes[0][1] > 1000 and sizes[1][1] > 0

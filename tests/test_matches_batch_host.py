@@ -116,6 +116,42 @@ def test_numpy_statement_names_the_sequence_with_a_frame_outside():
         mb.match_tables_batch_np(seqs)
 
 
+def test_the_edge_sets_are_what_they_say():
+    """the sets tests/test_gpu_matches_batch.py gives the single entry points: every claimed property, by the model"""
+    K = 20
+    for n_points, seq in mb.EDGE_SETS.items():
+        off, frames, xy, labels, n_img = seq
+        lengths = np.diff(off).tolist()
+        assert sum(lengths) == len(frames) == n_points and (n_points == 1 or set(mb.EDGE_LENGTHS) <= set(lengths))
+        runs = [frames[a:b] for a, b in zip(off[:-1], off[1:])]
+        assert all(len(set(r.tolist())) == len(r) for r in runs)
+        if n_points > 1:
+            assert any((np.diff(r) < 0).any() for r in runs) and any((np.abs(np.diff(np.sort(r))) > 1).any() for r in runs)
+            assert 0.15 < labels.mean() < 0.45
+        # all points kept: the lengths are the kept lengths -- 41 emits 20 matches at j = 40 (40 % 2 == 0, 40 // 2 >= 20) and 19 at j = 0
+        assert len(single_tables(seq, False)[5]) == mb.n_matches_np(lengths, K)
+        kept = [int((~labels[a:b]).sum()) for a, b in zip(off[:-1], off[1:])]
+        assert len(single_tables(seq, True)[5]) == mb.n_matches_np(kept, K)
+        assert (mb.n_matches_np(lengths, K) > 0) == (mb.n_matches_np(kept, K) > 0) == (n_points > 1)
+    assert mb.n_matches_np([41], K) == 41 * K - 20 and mb.n_matches_np([40], K) == 40 * K - 20 and mb.n_matches_np([21], K) == 21 * K - 20
+    assert mb.n_matches_np([20], K) == 380 and mb.n_matches_np([2], K) == 2 and mb.n_matches_np([1], K) == 0
+    off, frames, xy, labels, n_img = mb.ALL_DYNAMIC_SET
+    assert len(frames) == 257 and labels.all()
+    got = single_tables(mb.ALL_DYNAMIC_SET, True)
+    assert len(got[1]) == 0 and len(got[5]) == 0 and not got[0].any() and len(got[0]) == n_img + 1
+    assert len(single_tables(mb.ALL_DYNAMIC_SET, False)[5]) == mb.n_matches_np(np.diff(off).tolist(), K) > 1000
+    for n_img, seq in mb.N_IMG_SETS.items():
+        off, frames, xy, labels, _ = seq
+        assert seq[4] == n_img and frames.min() == 0 and frames.max() == n_img - 1 and not labels.any()
+        kp_off, kp_xy, pair_key, pair_off, pair_first, rows = single_tables(seq, True)
+        assert len(kp_off) == n_img + 1 and len(kp_xy) == len(frames)
+        assert (len(rows) > 0) == (n_img > 1) and len(rows) == mb.n_matches_np(np.diff(off).tolist(), K)
+        if n_img > 1:
+            assert (n_img - 1) * n_img in pair_key.tolist()                       # (last image, image 0)
+            assert mb.bits_np(n_img) == {2: 1, 255: 8, 256: 8, 257: 9}[n_img]
+            assert (int(pair_key.max()) >= 2 ** 16) == (n_img == 257) and mb.bits_np(n_img * n_img) == {2: 2, 255: 16, 256: 16, 257: 17}[n_img]
+
+
 # ---- 2. the header against the statement ------------------------------------------------------------------------------------------
 
 def test_the_bounds(host):
@@ -161,7 +197,7 @@ def test_key_codec_and_width_check(host):
         bits = host.psfm_host_mtb_key_bits(n_seq, rng_local, ctypes.byref(lb))
         w_bits, w_lb = mb.key_bits_np(n_seq, rng_local)
         assert (bits, lb.value) == (w_bits, w_lb) and bits > 0 and (1 << lb.value) >= rng_local
-        assert bits == mb.bits_np(rng_local) + mb.bits_np(n_seq) <= 64
+        assert bits == mb.bits_np(rng_local) + (mb.bits_np(n_seq) if n_seq > 1 else 0) <= 64
         for _ in range(200):
             b, local = int(rng.integers(0, n_seq)), int(rng.integers(0, rng_local))
             key = host.psfm_host_mtb_key(b, local, lb.value)
@@ -174,6 +210,24 @@ def test_key_codec_and_width_check(host):
         assert host.psfm_host_mtb_key_bits(n_seq, rng_local, ctypes.byref(lb)) == 0 == mb.key_bits_np(n_seq, rng_local)[0], (n_seq, rng_local)
     for v in (0, 1, 2, 3, 4, 5, 255, 256, 257, 2 ** 32, 2 ** 63, 2 ** 64 - 1):
         assert host.psfm_host_mtb_bits(v) == mb.bits_np(v)
+
+
+def test_one_sequence_spends_no_key_bit_on_the_sequence(host):
+    """psfm_mtb_key_bits(1, r): the composed key of a single call is the local key, psfm_mtb_bits(r) bits wide"""
+    lb = ctypes.c_int(0)
+    for p in range(0, 64):
+        for r in (2 ** p - 1, 2 ** p, 2 ** p + 1):
+            if r < 1 or (p == 63 and r > 2 ** 63):
+                continue
+            bits = host.psfm_host_mtb_key_bits(1, r, ctypes.byref(lb))
+            assert bits == lb.value == host.psfm_host_mtb_bits(r) == mb.bits_np(r) < 64, r
+            assert (bits, lb.value) == mb.key_bits_np(1, r)
+            assert host.psfm_host_mtb_key(0, r - 1, lb.value) == r - 1                  # sequence 0 leaves the local key as it is
+            # two sequences still pay their bit
+            assert host.psfm_host_mtb_key_bits(2, r, ctypes.byref(lb)) == (bits + 1 if bits < 64 else 0)
+    # a local key that needs all 64 bits is refused even for one sequence (the shift of psfm_mtb_key)
+    for r in (2 ** 63 + 1, 2 ** 64 - 1):
+        assert host.psfm_host_mtb_key_bits(1, r, ctypes.byref(lb)) == 0 == mb.key_bits_np(1, r)[0]
 
 
 GROUP_CASES = {
