@@ -9,6 +9,7 @@
 #include <stdlib.h>
 
 #include "psfm_internal.h"
+#include "psfm_solve_policy.h"
 
 static thread_local char g_err[512] = "";
 // The per-device gate of psfm_internal.h (the one piece of process-wide state in the library, documented in psfm.h).
@@ -462,26 +463,303 @@ psfm_status psfm_track_alloc(psfm_ctx* c, const PsfmTrackDims& d)
     return PSFM_OK;
 }
 
-// Occlusion maps produced on a side stream while the frame loop consumes them (psfm_connect): one event per chunk
-// of frame pairs; the loop waits for the chunk that contains the pair it is about to read.
-struct PsfmOccPipeline {
-    int chunk = 0;                       // frame pairs per chunk (0 = maps already complete)
-    std::vector<hipEvent_t> ready;       // stride-1 maps: chunk c covers pairs [c*chunk, (c+1)*chunk)
-    std::vector<hipEvent_t> ready_s2;    // stride-2 maps
-    int waited = -1, waited_s2 = -1;
-    psfm_status need(int pair, bool s2, hipStream_t s)
-    {
-        if (chunk <= 0) return PSFM_OK;
-        std::vector<hipEvent_t>& ev = s2 ? ready_s2 : ready;
-        int& w = s2 ? waited_s2 : waited;
-        const int cidx = pair / chunk;
-        while (w < cidx && w + 1 < (int)ev.size()) {
-            ++w;
-            PSFM_HIP(hipStreamWaitEvent(s, ev[w], 0));
-        }
-        return PSFM_OK;
+// ---- track mode: the whole recurrence as ONE persistent launch when every lane can be resident at once ----
+// *done = true: the run stayed -- the result and `info` are complete.  PSFM_OK with *done = false: not tried, refused or given up
+// (fall back): the caller runs per-frame launches.
+static psfm_status psfm_track_persistent(psfm_ctx* c, const PsfmTrackDims& d, const float* flows, const uint8_t* occ, int64_t occ_pitch,
+                                         const float* fuse_flows_b, float fuse_thres, bool device_is_ours, PsfmOccPipeline* pipe,
+                                         psfm_track_info* info, hipStream_t s, bool* done)
+{
+    *done = false;
+    const int n_flows = d.n_flows;
+    const int64_t P = (int64_t)d.H * d.W;
+    psfm_status st;
+    const int maxb = psfm_persist_max_blocks(c);
+    const int64_t need_blocks = (d.G + 255) / 256;
+    if (!(maxb > 0 && need_blocks <= maxb && device_is_ours)) return PSFM_OK;   // (not ours: another psfm call is in flight on this device)
+    PsfmTrackDims dp = d;
+    // spare lanes for tracks born faster than lanes come back (alive tracks can exceed the grid where flows
+    // converge): twice the grid while that is cheap, a quarter more otherwise, never more than fits the device
+    int64_t nb = need_blocks <= 256 ? 2 * need_blocks + 4 : need_blocks + need_blocks / 4;
+    dp.nblk = (int)(nb < maxb ? nb : maxb);
+    // fused flow_check: the occlusion maps are computed by whatever blocks exist -- enough of them to cover the
+    // image in one round of 1024-pixel chunks (blocks without grid points only check flows and lend lanes)
+    if (fuse_flows_b) {
+        const int64_t fc_blocks = (P + 1023) / 1024;
+        const int64_t want = fc_blocks < maxb ? fc_blocks : maxb;
+        if (want > dp.nblk) dp.nblk = (int)want;
     }
+    dp.cap = (int64_t)dp.nblk * (256 + psfm_persist_guests());   // log columns: thread lanes, then guest lanes
+    dp.nsh = dp.nblk < PSFM_NSHARD ? dp.nblk : PSFM_NSHARD;
+    dp.free_cap = (int)(((dp.nblk + dp.nsh - 1) / dp.nsh) * 256) + 1024;
+    dp.seg_cap = (int)(d.traj_cap / dp.nblk) + 64;
+    dp.spill_cap = (int)(d.traj_cap / 8) + 4096;
+    const int64_t fin_total = (int64_t)dp.nblk * dp.seg_cap + dp.spill_cap;
+    if ((st = c->log.ensure(sizeof(double2) * (size_t)(n_flows + 1) * dp.cap)) != PSFM_OK) return st;
+    if ((st = c->free_stack.ensure(sizeof(int) * (size_t)dp.free_cap * PSFM_NSHARD * 2)) != PSFM_OK) return st;
+    if ((st = c->fin_keys.ensure(sizeof(unsigned long long) * fin_total)) != PSFM_OK) return st;
+    if ((st = c->fin_lanes.ensure(sizeof(int) * fin_total)) != PSFM_OK) return st;
+    if ((st = c->handoff.ensure((size_t)dp.nblk * 256 * 24)) != PSFM_OK) return st;
+    if ((st = c->seg_info.ensure(sizeof(int) * 2 * (size_t)dp.nblk)) != PSFM_OK) return st;
+    if ((st = c->persist_bar.ensure((size_t)(4 * PSFM_NSHARD + 1) * 128)) != PSFM_OK) return st;
+    if ((st = c->place_tab.ensure(psfm_place_table_bytes(dp))) != PSFM_OK) return st;
+    if (pipe && (st = pipe->need(n_flows - 1, false, s)) != PSFM_OK) return st;   // every occlusion map
+    bool fallback = false;
+    const bool trace = getenv("PSFM_TRACE") != nullptr;
+    const auto t1 = std::chrono::steady_clock::now();
+    st = psfm_launch_chain_persist(c, dp, flows, occ, occ_pitch, fuse_flows_b, fuse_thres, s);
+    if (st == PSFM_ERR_CAPACITY) {      // the cooperative launch was refused: per-frame launches
+        fallback = true;
+        st = PSFM_OK;
+    } else {
+        if (st != PSFM_OK) return st;
+        c->prof.begin(PSFM_PROF_FINALIZE, s);
+        st = psfm_finalize_persist(c, dp, &fallback, s);
+        c->prof.end(s);
+    }
+    if (trace) {
+        const auto t2 = std::chrono::steady_clock::now();
+        fprintf(stderr, "[psfm %p] persistent loop: launch+finalize %.2f ms, fallback %d, overflow %d\n", (void*)c,
+                std::chrono::duration<double, std::milli>(t2 - t1).count(), (int)fallback,
+                ((PsfmCounters*)c->host_pinned)->overflow);
+    }
+    if (st != PSFM_OK) return st;
+    if (!fallback) PSFM_HIP(hipStreamSynchronize(s));
+    c->prof.collect();
+    if (!fallback) psfm_fill_track_info(info, c, dp.cap, 0, 2);
+    *done = !fallback;
+    return PSFM_OK;
+}
+
+// The maps the per-frame launches read when the persistent loop did not produce them: the occlusion maps of psfm_connect's fused
+// form, stand-alone, and the kill maps of the motion-boundary option.
+static psfm_status psfm_track_maps(psfm_ctx* c, const PsfmTrackDims& d, const float* flows, const uint8_t* occ, int64_t occ_pitch,
+                                   const float* fuse_flows_b, float fuse_thres, PsfmOccPipeline* pipe, hipStream_t s)
+{
+    const int n_flows = d.n_flows, h = d.H, w = d.W;
+    const int64_t P = (int64_t)h * w;
+    psfm_status st;
+    if (fuse_flows_b) {   // the persistent loop did not run (or gave up): the maps it would have produced, stand-alone
+        c->prof.begin(PSFM_PROF_FLOW_CHECK, s);
+        for (int f = 0; f < n_flows; ++f)
+            if ((st = psfm_launch_flow_check(flows + (size_t)f * P * 2, fuse_flows_b + (size_t)f * P * 2, 1, h, w, fuse_thres,
+                                             const_cast<uint8_t*>(occ) + (size_t)f * occ_pitch, nullptr, s)) != PSFM_OK) return st;
+        c->prof.end(s);
+    }
+    if (c->mb_enable) {
+        // the kill maps of the sequence -- bit 0 the occlusion map, bit 1 motion_boundary(flow) -- in ONE launch, from the COMPLETE
+        // occlusion maps (psfm_connect: every chunk of the side stream; the stride-2 maps keep their pipeline).  `occ` stays 0/1.
+        if ((st = c->kill.ensure((size_t)n_flows * (size_t)P)) != PSFM_OK) return st;
+        if (pipe && (st = pipe->need(n_flows - 1, false, s)) != PSFM_OK) return st;
+        if (occ_pitch != P) { psfm_set_error("psfm_track: motion boundary needs densely packed occlusion maps"); return PSFM_ERR_ARG; }
+        if ((st = psfm_launch_motion_boundary(flows, occ, n_flows, h, w, c->mb_thres, c->kill.as<uint8_t>(), s)) != PSFM_OK) return st;
+    }
+    return PSFM_OK;
+}
+
+namespace {
+// The state of one run of the recurrence as per-frame launches (psfm_track_impl): what the frame loop, its windows and its
+// checkpoints share.
+struct PsfmFrameRun {
+    psfm_ctx* c; const PsfmTrackDims& d; hipStream_t s; PsfmGate& gate; PsfmOccPipeline* pipe;
+    const float* flows; const uint8_t* occ; int64_t occ_pitch; const float* flows_f2; const uint8_t* occ_s2;
+    int64_t P;                    // pixels per map
+    int n_flows;
+    bool optimize, mb;
+    int check = 16;               // frames between two host checkpoints
+    int unroll_fixed = 0;         // PSFM_SOLVE_UNROLL
+    bool merge = true;            // chain step and fused solve of a frame as ONE launch
+    bool seq_ok = false;          // fused windows are device-paced
+    std::vector<psfm_solve_stats> hstats;
+    int first_unchecked = 1;      // first solve whose statistics have not been folded in
+    int64_t total_iters = 0;
+    int launch_id = 0;           // device-paced windows: id of the next psfm_seq_kernel launch (== PsfmCounters::pc_owner)
+    int idle_windows = 0;         // ... consecutive windows in which no frame completed (the device inside one long solve)
+    bool pc_in_step = true;       // the device's program counter is where the host thinks it is (track_init: frame 1, launch 0)
+
+    PsfmSolveMaps maps(int f) const { return psfm_solve_maps(flows, flows_f2, occ_s2, P, f); }
+    bool fused_now() const { return c->solver_mode == 2 || (c->solver_mode == 0 && c->solve_mode == 0); }
+    psfm_status begin();
+    psfm_status checkpoint(int f_hi, bool fused_now, bool seq, int* f_next);
+    psfm_status window_device_paced(int* f);
+    psfm_status frame_host_paced(int* f, bool fused_now);
 };
+
+// Frame loop.  In track_optimize mode nothing returns to the host inside a window of `check` frames: each
+// solve is enqueued with `solve_unroll` iterations; a solve that needs more raises a device-side stall flag that
+// turns every later launch into a no-op, and the checkpoint below resumes it and re-enqueues from there.
+psfm_status PsfmFrameRun::begin()
+{
+    psfm_status st;
+    // frames between two host checkpoints (every checkpoint drains the queue).  Round 1 (150 us per frame): 8 -> 16 gained
+    // 1.5 %, 32 nothing more; PSFM_CHECK_FRAMES overrides for measurements
+    static const int check_env = getenv("PSFM_CHECK_FRAMES") ? atoi(getenv("PSFM_CHECK_FRAMES")) : 0;
+    check = check_env >= 2 ? check_env : 16;
+    hstats.resize((size_t)n_flows + 1);
+    if (optimize) {
+        if ((st = c->sol_stats.ensure(sizeof(psfm_solve_stats) * (size_t)(n_flows + 1))) != PSFM_OK) return st;
+    }
+    // (tests: PSFM_SOLVE_UNROLL=1 makes every solve that needs more than two iterations stall and resume)
+    const char* unroll_env = getenv("PSFM_SOLVE_UNROLL");
+    unroll_fixed = unroll_env ? (atoi(unroll_env) < 1 ? 1 : atoi(unroll_env)) : 0;
+    // How a frame's solve is enqueued (psfm_ctx_set_solver): the fused solve -- ONE launch that speculates solve_K
+    // Gauss-Newton iterations -- or the launch chain (init + solve_unroll iterations + write-back).  Adaptive: the rules of
+    // psfm_solve_policy.h, window by window.
+    if (optimize && (st = psfm_solve_prepare(c, d, s)) != PSFM_OK) return st;
+    // PSFM_MERGE_FRAME=0: chain step and fused solve as two launches (what the merged frame kernel is measured against);
+    // PSFM_SEQ=0: host-paced frame kernels (one per frame, stall + redo when a solve needs more iterations than speculated)
+    static const bool merge_env = !(getenv("PSFM_MERGE_FRAME") && atoi(getenv("PSFM_MERGE_FRAME")) == 0);
+    merge = merge_env;
+    const bool seq_env = !(getenv("PSFM_SEQ") && atoi(getenv("PSFM_SEQ")) == 0);
+    // (motion boundary: the two-launch frame -- the merged and the device-paced kernels do not form the second verdict)
+    seq_ok = optimize && merge && seq_env && unroll_fixed == 0 && !mb;
+    return PSFM_OK;
+}
+
+// One checkpoint: counters + the window's statistics to the host, the stalled solve (if any) redone, statistics folded
+// into the result and into the adaptation of mode / K / unroll.  f_hi: last frame whose launch has been enqueued.
+// Returns the first frame that is NOT complete in *f_next.
+psfm_status PsfmFrameRun::checkpoint(int f_hi, bool fused_now, bool seq, int* f_next)
+{
+    PsfmCounters* hc = (PsfmCounters*)c->host_pinned;
+    PSFM_HIP(hipMemcpyAsync(hc, c->counters.p, sizeof(PsfmCounters), hipMemcpyDeviceToHost, s));
+    PSFM_HIP(hipMemcpyAsync(hstats.data() + first_unchecked, c->sol_stats.as<psfm_solve_stats>() + first_unchecked,
+                            sizeof(psfm_solve_stats) * (size_t)(f_hi - first_unchecked + 1), hipMemcpyDeviceToHost, s));
+    PSFM_HIP(hipStreamSynchronize(s));
+    // Nothing of this call is in flight now.  If other psfm calls of the process wait for the device (this sequence holds it
+    // exclusively for its resident solves), let them in: the rest of the sequence runs its solves as launches, which overlap
+    // with other sequences -- a late-comer waits for one window of frames at most, not for the whole sequence.
+    if (gate.yield_exclusive()) c->pc_persist_ok = c->resident_budget > 0;
+    // A full table ends the sequence here: a launch behind that point counts on blocks the grid does not have (its solve never
+    // sees its last arrival: no stall flag, no progress), and finalize would refuse the result anyway.  The caller raises the
+    // capacity and runs the sequence again (the Python mirror does: trajectory.run_connect).
+    if ((hc->overflow & 7) != 0 || hc->n_lanes > d.cap) {
+        psfm_set_error("capacity exceeded: lanes used %d of %lld, overflow bits %d (frame %d of %d); raise psfm_ctx_set_capacity",
+                       hc->n_lanes, (long long)d.cap, hc->overflow, hc->pc_frame, n_flows);
+        return PSFM_ERR_CAPACITY;
+    }
+    const int kmax = psfm_solve_kmax();
+    const int stalled = hc->stall ? hc->stall - 1 : -1;   // (the redo below reuses the pinned block `hc` points at)
+    int last_ok = f_hi;
+    if (seq) {      // frames below the device's program counter are complete (it may be in the middle of the next solve)
+        const int pcf = hc->pc_frame < n_flows ? hc->pc_frame : n_flows;
+        last_ok = pcf - 1;
+    }
+    if (stalled >= 0) {
+        const int fs = stalled;
+        psfm_solve_stats ss;
+        memset(&ss, 0, sizeof(ss));
+        const PsfmSolveMaps m = maps(fs);
+        psfm_status st2 = psfm_solve_frame_resume(c, d, m.flow01, m.flow12, m.flow02, m.occ02, fs, &ss,
+                                                  psfm_resume_fused_k(fused_now, seq, c->solver_K, psfm_k_now(c->solver_K, c->solve_K), kmax),
+                                                  !fused_now, s);
+        if (st2 != PSFM_OK) return st2;
+        hstats[fs] = ss;
+        last_ok = fs;
+        pc_in_step = false;     // the device's counter still points at the redone frame
+    }
+    PsfmWindowTally tally;
+    for (int k = first_unchecked; k <= last_ok; ++k) {
+        tally.add(hstats[k], kmax);
+        if (hstats[k].termination >= 0) {   // -1: no track had a full buffer, nothing was solved
+            c->solve_stats.push_back(hstats[k]);
+            total_iters += hstats[k].iterations;
+            if (!fused_now) ++c->n_chain;
+            else if (k == stalled) ++c->n_fused_redone;
+            else ++c->n_fused_ok;
+        }
+    }
+    if (tally.n_solved > 0) {
+        c->solve_mode = tally.mode_next();
+        c->solve_K = seq ? tally.k_device_paced(kmax) : tally.k_host_paced(c->solve_K);
+    }
+    c->solve_unroll = tally.unroll_next(c->solve_unroll);
+    first_unchecked = last_ok + 1;
+    *f_next = last_ok + 1;   // after a stall: re-enqueue the (poisoned) frames behind the redone solve
+    return PSFM_OK;
+}
+
+// ---- a window of the device-paced sequence: launches that each do "the next thing" (psfm_seq_kernel) ----
+psfm_status PsfmFrameRun::window_device_paced(int* f_io)
+{
+    psfm_status st;
+    int f = *f_io;
+    int* hpc = (int*)((char*)c->host_pinned + 320);     // pinned staging for {pc_frame, pc_phase, pc_owner, solve_K}
+    PsfmCounters* dctr = c->counters.as<PsfmCounters>();
+    const int k_now = psfm_k_now(c->solver_K, c->solve_K);
+    if (!pc_in_step) {       // behind a host-paced window or a redo: put the device's counter where the host is
+        hpc[0] = f; hpc[1] = 0; hpc[2] = launch_id; hpc[3] = k_now;
+        PSFM_HIP(hipMemcpyAsync(&dctr->pc_frame, hpc, 4 * sizeof(int), hipMemcpyHostToDevice, s));
+        pc_in_step = true;
+    } else {
+        hpc[3] = k_now;
+        PSFM_HIP(hipMemcpyAsync(&dctr->solve_K, hpc + 3, sizeof(int), hipMemcpyHostToDevice, s));
+    }
+    const int n_launch = psfm_window_launches(n_flows - f, check);
+    const int f_hi = psfm_window_reach(f, n_launch, n_flows - 1);   // the furthest the device can get
+    if (pipe && (st = pipe->need(f_hi, false, s)) != PSFM_OK) return st;
+    if (pipe && (st = pipe->need(f_hi - 1, true, s)) != PSFM_OK) return st;
+    if ((st = psfm_launch_seq(c, d, flows, occ, occ_pitch, flows_f2, occ_s2, n_launch, launch_id, s)) != PSFM_OK) return st;
+    launch_id += n_launch;
+    const int f_before = f;
+    if ((st = checkpoint(f_hi, true, true, &f)) != PSFM_OK) return st;
+    *f_io = f;
+    if (f != f_before) { idle_windows = 0; return PSFM_OK; }
+    // No frame completed and no solve stalled: the device is INSIDE the solve of frame f -- every iteration so far accepted,
+    // none terminating, the window's launches used up (a sequence's last frame has three: K + 2 + 2 iterations).  Its chain
+    // step has run: the next window's launches go on with the solve (at PC_KMAX accepted iterations it stalls and is redone
+    // at the checkpoint).  Running the frame from the top here -- what rounds 2-4 did, "never expected" -- gave birth to the frame's
+    // newborns twice (found by scripts/stress_batch.py in round 5: a two-flow sequence whose one solve takes 8 iterations).
+    if (getenv("PSFM_TRACE")) {
+        const PsfmCounters* hc = (const PsfmCounters*)c->host_pinned;
+        unsigned tk[8] = {0};
+        if (c->sol_fused.p) (void)hipMemcpy(tk, c->sol_fused.p, sizeof(tk), hipMemcpyDeviceToHost);
+        fprintf(stderr, "[psfm %p] device-paced window without a completed frame: host frame %d, next launch %d; device pc {frame %d, phase %d, "
+                "owner %d, K %d}, lanes %d (snapshots %d %d), stall %d, overflow %d, tickets %u %u %u %u\n", (void*)c, f, launch_id,
+                hc->pc_frame, hc->pc_phase, hc->pc_owner, hc->solve_K, hc->n_lanes, hc->n_lanes_snap[0], hc->n_lanes_snap[1], hc->stall,
+                hc->overflow, tk[0], tk[1], tk[2], tk[3]);
+    }
+    if (++idle_windows > 8) { psfm_set_error("psfm_track: the device-paced sequence made no progress in 8 windows (frame %d)", f); return PSFM_ERR_SOLVER; }
+    return PSFM_OK;
+}
+
+// A host-paced frame -- track.py:31-47 / track_optimize.py:31-50, one loop iteration:
+// one launch = births of frame f (new_traj_all) + chain step f (step_forward, extend_all); behind it the frame's solve, and the
+// checkpoint where a window ends
+psfm_status PsfmFrameRun::frame_host_paced(int* f_io, bool fused_now)
+{
+    psfm_status st;
+    const int f = *f_io;
+    pc_in_step = false;         // the device-side counter is not maintained
+    if (pipe && (st = pipe->need(f, false, s)) != PSFM_OK) return st;
+    const bool solve_now = optimize && f + 1 >= 2;   // track_optimize.py:49-50
+    const PsfmSolveMaps m = solve_now ? maps(f) : PsfmSolveMaps{nullptr, nullptr, nullptr, nullptr};
+    if (solve_now && fused_now && merge && !mb) {
+        // ONE launch: chain step of the frame + the fused solve of its tracks
+        if (pipe && (st = pipe->need(f - 1, true, s)) != PSFM_OK) return st;
+        st = psfm_launch_frame(c, d, m.flow01, m.flow12, m.flow02, occ + (size_t)f * occ_pitch, m.occ02, f, psfm_k_now(c->solver_K, c->solve_K), s);
+        if (st != PSFM_OK) return st;
+    } else {
+        if (mb) st = psfm_launch_chain_step_mb(c, d, flows + (size_t)f * P * 2, c->kill.as<uint8_t>() + (size_t)f * P, f, optimize, s);
+        else st = psfm_launch_chain_step(c, d, flows + (size_t)f * P * 2, occ + (size_t)f * occ_pitch, f, optimize, s);
+        if (st != PSFM_OK) return st;
+        if (solve_now) {
+            if (pipe && (st = pipe->need(f - 1, true, s)) != PSFM_OK) return st;
+            if (fused_now) {   // (timed inside: kernel begin / end events)
+                st = psfm_solve_frame_fused(c, d, m.flow01, m.flow12, m.flow02, m.occ02, f, psfm_k_now(c->solver_K, c->solve_K), s);
+            } else {
+                c->prof.begin(PSFM_PROF_SOLVER, s);
+                st = psfm_solve_frame_enqueue(c, d, m.flow01, m.flow12, m.flow02, m.occ02, f, unroll_fixed > 0 ? unroll_fixed : c->solve_unroll, s);
+                c->prof.end(s);
+            }
+            if (st != PSFM_OK) return st;
+        }
+    }
+    if (optimize && f >= 1 && ((f % check) == check - 1 || f == n_flows - 1)) return checkpoint(f, fused_now, false, f_io);
+    *f_io = f + 1;
+    return PSFM_OK;
+}
+}  // namespace
 
 static psfm_status psfm_track_impl(psfm_ctx* c, const float* flows, const uint8_t* occ, const float* flows_f2,
                                    const uint8_t* occ_s2, int n_flows, int h, int w, int ratio, psfm_track_info* info,
@@ -509,308 +787,23 @@ static psfm_status psfm_track_impl(psfm_ctx* c, const float* flows, const uint8_
     const int64_t P = (int64_t)h * w;
     if ((st = psfm_track_alloc(c, d)) != PSFM_OK) return st;
 
-    c->solve_stats.clear();
-    c->res_n_traj = c->res_n_points = 0;
-    c->res_n_flows = n_flows;
-    c->res_is_query = false;
-    c->pc_persist_ok = device_is_ours || c->resident_budget > 0;
-    c->pc_giveups = 0;
+    psfm_call_begin(c, n_flows, device_is_ours || c->resident_budget > 0);
 
-    // ---- track mode: the whole recurrence as ONE persistent launch when every lane can be resident at once ----
     const bool mb = c->mb_enable;     // psfm_ctx_set_motion_boundary: per-frame launches with the second verdict, whatever the chain mode
     if (!optimize && c->chain_mode != 1 && !mb) {
-        const int maxb = psfm_persist_max_blocks(c);
-        const int64_t need_blocks = (d.G + 255) / 256;
-        if (maxb > 0 && need_blocks <= maxb && device_is_ours) {   // (not ours: another psfm call is in flight on this device)
-            PsfmTrackDims dp = d;
-            // spare lanes for tracks born faster than lanes come back (alive tracks can exceed the grid where flows
-            // converge): twice the grid while that is cheap, a quarter more otherwise, never more than fits the device
-            int64_t nb = need_blocks <= 256 ? 2 * need_blocks + 4 : need_blocks + need_blocks / 4;
-            dp.nblk = (int)(nb < maxb ? nb : maxb);
-            // fused flow_check: the occlusion maps are computed by whatever blocks exist -- enough of them to cover the
-            // image in one round of 1024-pixel chunks (blocks without grid points only check flows and lend lanes)
-            if (fuse_flows_b) {
-                const int64_t fc_blocks = (P + 1023) / 1024;
-                const int64_t want = fc_blocks < maxb ? fc_blocks : maxb;
-                if (want > dp.nblk) dp.nblk = (int)want;
-            }
-            dp.cap = (int64_t)dp.nblk * (256 + psfm_persist_guests());   // log columns: thread lanes, then guest lanes
-            dp.nsh = dp.nblk < PSFM_NSHARD ? dp.nblk : PSFM_NSHARD;
-            dp.free_cap = (int)(((dp.nblk + dp.nsh - 1) / dp.nsh) * 256) + 1024;
-            dp.seg_cap = (int)(d.traj_cap / dp.nblk) + 64;
-            dp.spill_cap = (int)(d.traj_cap / 8) + 4096;
-            const int64_t fin_total = (int64_t)dp.nblk * dp.seg_cap + dp.spill_cap;
-            if ((st = c->log.ensure(sizeof(double2) * (size_t)(n_flows + 1) * dp.cap)) != PSFM_OK) return st;
-            if ((st = c->free_stack.ensure(sizeof(int) * (size_t)dp.free_cap * PSFM_NSHARD * 2)) != PSFM_OK) return st;
-            if ((st = c->fin_keys.ensure(sizeof(unsigned long long) * fin_total)) != PSFM_OK) return st;
-            if ((st = c->fin_lanes.ensure(sizeof(int) * fin_total)) != PSFM_OK) return st;
-            if ((st = c->handoff.ensure((size_t)dp.nblk * 256 * 24)) != PSFM_OK) return st;
-            if ((st = c->seg_info.ensure(sizeof(int) * 2 * (size_t)dp.nblk)) != PSFM_OK) return st;
-            if ((st = c->persist_bar.ensure((size_t)(4 * PSFM_NSHARD + 1) * 128)) != PSFM_OK) return st;
-            if ((st = c->place_tab.ensure(psfm_place_table_bytes(dp))) != PSFM_OK) return st;
-            if (pipe && (st = pipe->need(n_flows - 1, false, s)) != PSFM_OK) return st;   // every occlusion map
-            bool fallback = false;
-            {
-                const bool trace = getenv("PSFM_TRACE") != nullptr;
-                const auto t1 = std::chrono::steady_clock::now();
-                st = psfm_launch_chain_persist(c, dp, flows, occ, occ_pitch, fuse_flows_b, fuse_thres, s);
-                if (st == PSFM_ERR_CAPACITY) {      // the cooperative launch was refused: per-frame launches below
-                    fallback = true;
-                    st = PSFM_OK;
-                } else {
-                    if (st != PSFM_OK) return st;
-                    c->prof.begin(PSFM_PROF_FINALIZE, s);
-                    st = psfm_finalize_persist(c, dp, &fallback, s);
-                    c->prof.end(s);
-                }
-                if (trace) {
-                    const auto t2 = std::chrono::steady_clock::now();
-                    fprintf(stderr, "[psfm %p] persistent loop: launch+finalize %.2f ms, fallback %d, overflow %d\n", (void*)c,
-                            std::chrono::duration<double, std::milli>(t2 - t1).count(), (int)fallback,
-                            ((PsfmCounters*)c->host_pinned)->overflow);
-                }
-            }
-            if (st != PSFM_OK) return st;
-            if (!fallback) {
-                PSFM_HIP(hipStreamSynchronize(s));
-                c->prof.collect();
-                if (info) {
-                    memset(info, 0, sizeof(*info));
-                    info->n_traj = c->res_n_traj;
-                    info->n_points = c->res_n_points;
-                    info->n_lanes_peak = ((PsfmCounters*)c->host_pinned)->n_lanes;
-                    info->lane_capacity = dp.cap;
-                    info->chain_mode = 2;
-                }
-                return PSFM_OK;
-            }
-            c->prof.collect();
-        }
+        bool done = false;
+        if ((st = psfm_track_persistent(c, d, flows, occ, occ_pitch, fuse_flows_b, fuse_thres, device_is_ours, pipe, info, s, &done)) != PSFM_OK) return st;
+        if (done) return PSFM_OK;
     }
-    if (fuse_flows_b) {   // the persistent loop did not run (or gave up): the maps it would have produced, stand-alone
-        c->prof.begin(PSFM_PROF_FLOW_CHECK, s);
-        for (int f = 0; f < n_flows; ++f)
-            if ((st = psfm_launch_flow_check(flows + (size_t)f * P * 2, fuse_flows_b + (size_t)f * P * 2, 1, h, w, fuse_thres,
-                                             const_cast<uint8_t*>(occ) + (size_t)f * occ_pitch, nullptr, s)) != PSFM_OK) return st;
-        c->prof.end(s);
-    }
-    if (mb) {
-        // the kill maps of the sequence -- bit 0 the occlusion map, bit 1 motion_boundary(flow) -- in ONE launch, from the COMPLETE
-        // occlusion maps (psfm_connect: every chunk of the side stream; the stride-2 maps keep their pipeline).  `occ` stays 0/1.
-        if ((st = c->kill.ensure((size_t)n_flows * (size_t)P)) != PSFM_OK) return st;
-        if (pipe && (st = pipe->need(n_flows - 1, false, s)) != PSFM_OK) return st;
-        if (occ_pitch != P) { psfm_set_error("psfm_track: motion boundary needs densely packed occlusion maps"); return PSFM_ERR_ARG; }
-        if ((st = psfm_launch_motion_boundary(flows, occ, n_flows, h, w, c->mb_thres, c->kill.as<uint8_t>(), s)) != PSFM_OK) return st;
-    }
+    if ((st = psfm_track_maps(c, d, flows, occ, occ_pitch, fuse_flows_b, fuse_thres, pipe, s)) != PSFM_OK) return st;
     if ((st = psfm_launch_track_init(c, d, s)) != PSFM_OK) return st;
-    int64_t total_iters = 0;
-    // Frame loop.  In track_optimize mode nothing returns to the host inside a window of PSFM_CHECK frames: each
-    // solve is enqueued with `solve_unroll` iterations; a solve that needs more raises a device-side stall flag that
-    // turns every later launch into a no-op, and the checkpoint below resumes it and re-enqueues from there.
-    // frames between two host checkpoints (every checkpoint drains the queue).  Round 1 (150 us per frame): 8 -> 16 gained
-    // 1.5 %, 32 nothing more; PSFM_CHECK_FRAMES overrides for measurements
-    static const int check_env = getenv("PSFM_CHECK_FRAMES") ? atoi(getenv("PSFM_CHECK_FRAMES")) : 0;
-    const int PSFM_CHECK = check_env >= 2 ? check_env : 16;
-    std::vector<psfm_solve_stats> hstats((size_t)n_flows + 1);
-    int first_unchecked = 1;
-    if (optimize) {
-        if ((st = c->sol_stats.ensure(sizeof(psfm_solve_stats) * (size_t)(n_flows + 1))) != PSFM_OK) return st;
-    }
-    // (tests: PSFM_SOLVE_UNROLL=1 makes every solve that needs more than two iterations stall and resume)
-    const char* unroll_env = getenv("PSFM_SOLVE_UNROLL");
-    const int unroll_fixed = unroll_env ? (atoi(unroll_env) < 1 ? 1 : atoi(unroll_env)) : 0;
-    // How a frame's solve is enqueued (psfm_ctx_set_solver): the fused solve -- ONE launch that speculates solve_K
-    // Gauss-Newton iterations -- or the launch chain (init + solve_unroll iterations + write-back).  Adaptive: a
-    // window (the frames between two checkpoints) whose solves rejected steps / left the Gauss-Newton path sends the next
-    // window to the chain, a clean window brings the fused solve back; solve_K follows the accepted steps seen.
-    c->n_fused_ok = c->n_fused_redone = c->n_chain = 0;
-    c->n_resident = c->n_iter_launches = 0;
-    if (optimize && (st = psfm_solve_prepare(c, d, s)) != PSFM_OK) return st;
-    // PSFM_MERGE_FRAME=0: chain step and fused solve as two launches (what the merged frame kernel is measured against);
-    // PSFM_SEQ=0: host-paced frame kernels (one per frame, stall + redo when a solve needs more iterations than speculated)
-    static const bool merge = !(getenv("PSFM_MERGE_FRAME") && atoi(getenv("PSFM_MERGE_FRAME")) == 0);
-    const bool seq_env = !(getenv("PSFM_SEQ") && atoi(getenv("PSFM_SEQ")) == 0);
-    // (motion boundary: the two-launch frame -- the merged and the device-paced kernels do not form the second verdict)
-    bool seq_ok = optimize && merge && seq_env && unroll_fixed == 0 && !mb;
-    int launch_id = 0;            // device-paced windows: id of the next psfm_seq_kernel launch (== PsfmCounters::pc_owner)
-    int idle_windows = 0;         // ... consecutive windows in which no frame completed (the device inside one long solve)
-    bool pc_in_step = true;       // the device's program counter is where the host thinks it is (track_init: frame 1, launch 0)
-    int* hpc = (int*)((char*)c->host_pinned + 320);     // pinned staging for {pc_frame, pc_phase, pc_owner, solve_K}
-    PsfmCounters* dctr = c->counters.as<PsfmCounters>();
-
-    // One checkpoint: counters + the window's statistics to the host, the stalled solve (if any) redone, statistics folded
-    // into the result and into the adaptation of mode / K / unroll.  f_hi: last frame whose launch has been enqueued.
-    // Returns the first frame that is NOT complete in *f_next.
-    auto checkpoint = [&](int f_hi, bool fused_now, bool seq, int* f_next) -> psfm_status {
-        PsfmCounters* hc = (PsfmCounters*)c->host_pinned;
-        PSFM_HIP(hipMemcpyAsync(hc, c->counters.p, sizeof(PsfmCounters), hipMemcpyDeviceToHost, s));
-        PSFM_HIP(hipMemcpyAsync(hstats.data() + first_unchecked, c->sol_stats.as<psfm_solve_stats>() + first_unchecked,
-                                sizeof(psfm_solve_stats) * (size_t)(f_hi - first_unchecked + 1), hipMemcpyDeviceToHost, s));
-        PSFM_HIP(hipStreamSynchronize(s));
-        // Nothing of this call is in flight now.  If other psfm calls of the process wait for the device (this sequence holds it
-        // exclusively for its resident solves), let them in: the rest of the sequence runs its solves as launches, which overlap
-        // with other sequences -- a late-comer waits for one window of frames at most, not for the whole sequence.
-        if (gate.yield_exclusive()) c->pc_persist_ok = c->resident_budget > 0;
-        // A full table ends the sequence here: a launch behind that point counts on blocks the grid does not have (its solve never
-        // sees its last arrival: no stall flag, no progress), and finalize would refuse the result anyway.  The caller raises the
-        // capacity and runs the sequence again (the Python mirror does: trajectory.run_connect).
-        if ((hc->overflow & 7) != 0 || hc->n_lanes > d.cap) {
-            psfm_set_error("capacity exceeded: lanes used %d of %lld, overflow bits %d (frame %d of %d); raise psfm_ctx_set_capacity",
-                           hc->n_lanes, (long long)d.cap, hc->overflow, hc->pc_frame, n_flows);
-            return PSFM_ERR_CAPACITY;
-        }
-        const int stalled = hc->stall ? hc->stall - 1 : -1;   // (the redo below reuses the pinned block `hc` points at)
-        int last_ok = f_hi;
-        if (seq) {      // frames below the device's program counter are complete (it may be in the middle of the next solve)
-            const int pcf = hc->pc_frame < n_flows ? hc->pc_frame : n_flows;
-            last_ok = pcf - 1;
-        }
-        if (stalled >= 0) {
-            const int fs = stalled;
-            psfm_solve_stats ss;
-            memset(&ss, 0, sizeof(ss));
-            // (a fused solve that ran out of iterations is first retried with two iterations more; the chain
-            // takes what is left -- and every stalled solve of a chain window)
-            const int k_used = c->solver_K > 0 ? c->solver_K : c->solve_K;
-            psfm_status st2 = psfm_solve_frame_resume(c, d, flows + (size_t)(fs - 1) * P * 2, flows + (size_t)fs * P * 2,
-                                                      flows_f2 + (size_t)(fs - 1) * P * 2, occ_s2 + (size_t)(fs - 1) * P, fs, &ss,
-                                                      (fused_now && !seq && c->solver_K == 0 && k_used < psfm_solve_kmax())
-                                                          ? (k_used + 2 < psfm_solve_kmax() ? k_used + 2 : psfm_solve_kmax()) : 0,
-                                                      !fused_now, s);
-            if (st2 != PSFM_OK) return st2;
-            hstats[fs] = ss;
-            last_ok = fs;
-            pc_in_step = false;     // the device's counter still points at the redone frame
-        }
-        int max_it = 0, n_solved = 0, n_unclean = 0, k_need = 2;
-        for (int k = first_unchecked; k <= last_ok; ++k) {
-            // (termination 5 = Ceres' FAILURE: the reference ignores it, trajectory_optimize.cpp:81-82, and carries on
-            // with the positions it had -- so does the device; the caller sees it in the solve statistics)
-            if (hstats[k].termination >= 0) {   // -1: no track had a full buffer, nothing was solved
-                c->solve_stats.push_back(hstats[k]);
-                total_iters += hstats[k].iterations;
-                // "clean": every iteration but the terminating one took the Gauss-Newton step and was accepted --
-                // what the fused solve speculates; it then needs successful_steps + 1 iterations in its launch
-                const psfm_solve_stats& q = hstats[k];
-                const bool clean = q.dogleg_nonGN == 0 && q.termination != PSFM_TERM_FAILURE &&
-                                   (q.iterations == q.successful_steps + 1 ||
-                                    (q.termination == PSFM_TERM_GRADIENT_TOL && q.iterations == q.successful_steps)) &&
-                                   q.successful_steps + 1 <= psfm_solve_kmax();
-                ++n_solved;
-                if (!clean) ++n_unclean;
-                else if (q.successful_steps + 1 > k_need) k_need = q.successful_steps + 1;
-                if (!fused_now) ++c->n_chain;
-                else if (k == stalled) ++c->n_fused_redone;
-                else ++c->n_fused_ok;
-            }
-            if (hstats[k].iterations > max_it) max_it = hstats[k].iterations;
-        }
-        if (n_solved > 0) {
-            c->solve_mode = (n_unclean * 8 > n_solved) ? 1 : 0;
-            if (seq) {
-                // device-paced: an iteration more than speculated costs one more launch, not a redo -- follow the MOST COMMON
-                // need of the window instead of its maximum
-                int hist[16] = {0};
-                for (int k = first_unchecked; k <= last_ok; ++k)
-                    if (hstats[k].termination >= 0) ++hist[hstats[k].successful_steps + 1 < 15 ? hstats[k].successful_steps + 1 : 15];
-                int best = 2;
-                for (int q = 2; q <= psfm_solve_kmax(); ++q) if (hist[q] > hist[best]) best = q;
-                c->solve_K = best;
-            } else {
-                c->solve_K = k_need > c->solve_K ? k_need : c->solve_K - (c->solve_K - k_need + 1) / 2;
-            }
-        }
-        // adapt the unroll to what this sequence needs, within [4, 64]: a solve of k iterations needs k-1 pc_iter
-        // launches (pc_init does the first), so max+1 leaves two spare launches for the slowest solve seen in the
-        // window (a spare launch is a no-op that costs < 1 us behind another one; a solve that still runs out raises the stall flag)
-        int want = max_it + 1;
-        want = want < 4 ? 4 : (want > 64 ? 64 : want);
-        c->solve_unroll = want > c->solve_unroll ? want : c->solve_unroll - (c->solve_unroll - want + 1) / 2;   // decays all the way
-        first_unchecked = last_ok + 1;
-        *f_next = last_ok + 1;   // after a stall: re-enqueue the (poisoned) frames behind the redone solve
-        return PSFM_OK;
-    };
-
-    int f = 0;
-    while (f < n_flows) {
-        const bool fused_now = c->solver_mode == 2 || (c->solver_mode == 0 && c->solve_mode == 0);
-        if (seq_ok && fused_now && f >= 1) {
-            // ---- a window of the device-paced sequence: launches that each do "the next thing" (psfm_seq_kernel) ----
-            const int k_now = c->solver_K > 0 ? c->solver_K : c->solve_K;
-            if (!pc_in_step) {       // behind a host-paced window or a redo: put the device's counter where the host is
-                hpc[0] = f; hpc[1] = 0; hpc[2] = launch_id; hpc[3] = k_now;
-                PSFM_HIP(hipMemcpyAsync(&dctr->pc_frame, hpc, 4 * sizeof(int), hipMemcpyHostToDevice, s));
-                pc_in_step = true;
-            } else {
-                hpc[3] = k_now;
-                PSFM_HIP(hipMemcpyAsync(&dctr->solve_K, hpc + 3, sizeof(int), hipMemcpyHostToDevice, s));
-            }
-            const int left = n_flows - f;
-            const int n_launch = (left < PSFM_CHECK ? left : PSFM_CHECK) + 2;   // two spare: continuation launches of the window
-            const int f_hi = f + n_launch - 1 < n_flows - 1 ? f + n_launch - 1 : n_flows - 1;   // the furthest the device can get
-            if (pipe && (st = pipe->need(f_hi, false, s)) != PSFM_OK) return st;
-            if (pipe && (st = pipe->need(f_hi - 1, true, s)) != PSFM_OK) return st;
-            if ((st = psfm_launch_seq(c, d, flows, occ, occ_pitch, flows_f2, occ_s2, n_launch, launch_id, s)) != PSFM_OK) return st;
-            launch_id += n_launch;
-            const int f_before = f;
-            if ((st = checkpoint(f_hi, true, true, &f)) != PSFM_OK) return st;
-            if (f == f_before) {
-                // No frame completed and no solve stalled: the device is INSIDE the solve of frame f -- every iteration so far accepted,
-                // none terminating, the window's launches used up (a sequence's last frame has three: K + 2 + 2 iterations).  Its chain
-                // step has run: the next window's launches go on with the solve (at PC_KMAX accepted iterations it stalls and is redone
-                // above).  Running the frame from the top here -- what rounds 2-4 did, "never expected" -- gave birth to the frame's
-                // newborns twice (found by scripts/stress_batch.py in round 5: a two-flow sequence whose one solve takes 8 iterations).
-                if (getenv("PSFM_TRACE")) {
-                    const PsfmCounters* hc = (const PsfmCounters*)c->host_pinned;
-                    unsigned tk[8] = {0};
-                    if (c->sol_fused.p) (void)hipMemcpy(tk, c->sol_fused.p, sizeof(tk), hipMemcpyDeviceToHost);
-                    fprintf(stderr, "[psfm %p] device-paced window without a completed frame: host frame %d, next launch %d; device pc {frame %d, phase %d, "
-                            "owner %d, K %d}, lanes %d (snapshots %d %d), stall %d, overflow %d, tickets %u %u %u %u\n", (void*)c, f, launch_id,
-                            hc->pc_frame, hc->pc_phase, hc->pc_owner, hc->solve_K, hc->n_lanes, hc->n_lanes_snap[0], hc->n_lanes_snap[1], hc->stall,
-                            hc->overflow, tk[0], tk[1], tk[2], tk[3]);
-                }
-                if (++idle_windows > 8) { psfm_set_error("psfm_track: the device-paced sequence made no progress in 8 windows (frame %d)", f); return PSFM_ERR_SOLVER; }
-            } else {
-                idle_windows = 0;
-            }
-            continue;
-        }
-        pc_in_step = false;         // a host-paced frame: the device-side counter is not maintained
-        // track.py:31-47 / track_optimize.py:31-50, one loop iteration:
-        // one launch = births of frame f (new_traj_all) + chain step f (step_forward, extend_all)
-        if (pipe && (st = pipe->need(f, false, s)) != PSFM_OK) return st;
-        const bool solve_now = optimize && f + 1 >= 2;   // track_optimize.py:49-50
-        if (solve_now && fused_now && merge && !mb) {
-            // ONE launch: chain step of the frame + the fused solve of its tracks
-            if (pipe && (st = pipe->need(f - 1, true, s)) != PSFM_OK) return st;
-            st = psfm_launch_frame(c, d, flows + (size_t)(f - 1) * P * 2, flows + (size_t)f * P * 2, flows_f2 + (size_t)(f - 1) * P * 2,
-                                   occ + (size_t)f * occ_pitch, occ_s2 + (size_t)(f - 1) * P, f, c->solver_K > 0 ? c->solver_K : c->solve_K, s);
-            if (st != PSFM_OK) return st;
-        } else {
-            if (mb) st = psfm_launch_chain_step_mb(c, d, flows + (size_t)f * P * 2, c->kill.as<uint8_t>() + (size_t)f * P, f, optimize, s);
-            else st = psfm_launch_chain_step(c, d, flows + (size_t)f * P * 2, occ + (size_t)f * occ_pitch, f, optimize, s);
-            if (st != PSFM_OK) return st;
-            if (solve_now) {
-                if (pipe && (st = pipe->need(f - 1, true, s)) != PSFM_OK) return st;
-                if (fused_now) {   // (timed inside: kernel begin / end events)
-                    st = psfm_solve_frame_fused(c, d, flows + (size_t)(f - 1) * P * 2, flows + (size_t)f * P * 2,
-                                                flows_f2 + (size_t)(f - 1) * P * 2, occ_s2 + (size_t)(f - 1) * P, f,
-                                                c->solver_K > 0 ? c->solver_K : c->solve_K, s);
-                } else {
-                    c->prof.begin(PSFM_PROF_SOLVER, s);
-                    st = psfm_solve_frame_enqueue(c, d, flows + (size_t)(f - 1) * P * 2, flows + (size_t)f * P * 2,
-                                                  flows_f2 + (size_t)(f - 1) * P * 2, occ_s2 + (size_t)(f - 1) * P, f,
-                                                  unroll_fixed > 0 ? unroll_fixed : c->solve_unroll, s);
-                    c->prof.end(s);
-                }
-                if (st != PSFM_OK) return st;
-            }
-        }
-        if (optimize && f >= 1 && ((f % PSFM_CHECK) == PSFM_CHECK - 1 || f == n_flows - 1)) {
-            if ((st = checkpoint(f, fused_now, false, &f)) != PSFM_OK) return st;
-            continue;
-        }
-        ++f;
+    PsfmFrameRun R{c, d, s, gate, pipe, flows, occ, occ_pitch, flows_f2, occ_s2, P, n_flows, optimize, mb};
+    if ((st = R.begin()) != PSFM_OK) return st;
+    for (int f = 0; f < n_flows;) {
+        const bool fused_now = R.fused_now();
+        if (R.seq_ok && fused_now && f >= 1) st = R.window_device_paced(&f);
+        else st = R.frame_host_paced(&f, fused_now);
+        if (st != PSFM_OK) return st;
     }
     // the positions of the last fused solve are still in their iterate buffer (no chain step followed to move them)
     if (optimize && n_flows >= 2 && (st = psfm_solve_flush(c, d, n_flows - 1, s)) != PSFM_OK) return st;
@@ -820,16 +813,7 @@ static psfm_status psfm_track_impl(psfm_ctx* c, const float* flows, const uint8_
     if (st != PSFM_OK) return st;
     PSFM_HIP(hipStreamSynchronize(s));
     c->prof.collect();
-    if (info) {
-        memset(info, 0, sizeof(*info));
-        info->n_traj = c->res_n_traj;
-        info->n_points = c->res_n_points;
-        info->n_lanes_peak = ((PsfmCounters*)c->host_pinned)->n_lanes;
-        info->lane_capacity = d.cap;
-        info->solver_iterations = total_iters;
-        info->n_solves = (int32_t)c->solve_stats.size();
-        info->chain_mode = 1;
-    }
+    psfm_fill_track_info(info, c, d.cap, R.total_iters, 1);
     return PSFM_OK;
 }
 
@@ -890,10 +874,10 @@ extern "C" psfm_status psfm_connect(psfm_ctx* c, const float* flows_f, const flo
     if (!c->side_stream) PSFM_HIP(hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking));
     hipStream_t side = c->side_stream;
     // the side stream starts after whatever the caller enqueued on `stream` (the inputs)
-    hipEvent_t e_in = c->prof.get();
-    PSFM_HIP(hipEventRecord(e_in, s));
-    PSFM_HIP(hipStreamWaitEvent(side, e_in, 0));
-    PsfmOccPipeline pipe;
+    PsfmOccPipeline pipe(c);      // (its events go back to the pool when this call returns, however it ends)
+    pipe.start = c->prof.get();
+    PSFM_HIP(hipEventRecord(pipe.start, s));
+    PSFM_HIP(hipStreamWaitEvent(side, pipe.start, 0));
     // pairs per side-stream launch: 10 beside the chain step of track mode; 5 beside track_optimize's frame kernel (round 3:
     // 8.25 ms per 1080p sequence against 8.28-8.40 with 10 and 8.31-8.44 with 20)
     pipe.chunk = getenv("PSFM_FC_CHUNK") && atoi(getenv("PSFM_FC_CHUNK")) > 0 ? atoi(getenv("PSFM_FC_CHUNK")) : (optimize ? 5 : 10);
@@ -910,36 +894,24 @@ extern "C" psfm_status psfm_connect(psfm_ctx* c, const float* flows_f, const flo
         const int mult = getenv("PSFM_FC_BG_BLOCKS") ? atoi(getenv("PSFM_FC_BG_BLOCKS")) : 0;   // resident blocks per CU; 0: short-lived blocks
         cus *= mult > 0 ? mult : 0;
     }
+    // pairs [p0, p0 + np) of one stack on the side stream, and the event behind them (handed to the pipeline before it is recorded:
+    // it goes back to the pool with the others whatever fails)
+    auto chunk = [&](const float* ff, const float* fb, uint8_t* maps, int p0, int np, std::vector<hipEvent_t>& ready) -> psfm_status {
+        psfm_status r = (bg && p0 > 0) ? psfm_launch_flow_check_bg(ff + (size_t)p0 * P * 2, fb + (size_t)p0 * P * 2, np, h, w, thres, maps + (size_t)p0 * P, cus, side)
+                                       : psfm_launch_flow_check(ff + (size_t)p0 * P * 2, fb + (size_t)p0 * P * 2, np, h, w, thres, maps + (size_t)p0 * P, nullptr, side);
+        if (r != PSFM_OK) return r;
+        ready.push_back(c->prof.get());
+        PSFM_HIP(hipEventRecord(ready.back(), side));
+        return PSFM_OK;
+    };
     for (int p0 = 0; p0 < n_flows; p0 += pipe.chunk) {
-        const int np = n_flows - p0 < pipe.chunk ? n_flows - p0 : pipe.chunk;
-        if (bg && p0 > 0) st = psfm_launch_flow_check_bg(flows_f + (size_t)p0 * P * 2, flows_b + (size_t)p0 * P * 2, np, h, w, thres,
-                                                        occ + (size_t)p0 * P, cus, side);
-        else st = psfm_launch_flow_check(flows_f + (size_t)p0 * P * 2, flows_b + (size_t)p0 * P * 2, np, h, w, thres,
-                                         occ + (size_t)p0 * P, nullptr, side);
-        if (st != PSFM_OK) return st;
-        hipEvent_t e = c->prof.get();
-        PSFM_HIP(hipEventRecord(e, side));
-        pipe.ready.push_back(e);
+        if ((st = chunk(flows_f, flows_b, occ, p0, n_flows - p0 < pipe.chunk ? n_flows - p0 : pipe.chunk, pipe.ready)) != PSFM_OK) return st;
         // the stride-2 maps of the same time range follow their stride-1 chunk (needed one frame later)
-        if (p0 < n2) {
-            const int np2 = n2 - p0 < pipe.chunk ? n2 - p0 : pipe.chunk;
-            if (bg && p0 > 0) st = psfm_launch_flow_check_bg(flows_f2 + (size_t)p0 * P * 2, flows_b2 + (size_t)p0 * P * 2, np2, h, w, thres,
-                                                            occ_s2 + (size_t)p0 * P, cus, side);
-            else st = psfm_launch_flow_check(flows_f2 + (size_t)p0 * P * 2, flows_b2 + (size_t)p0 * P * 2, np2, h, w,
-                                             thres, occ_s2 + (size_t)p0 * P, nullptr, side);
-            if (st != PSFM_OK) return st;
-            hipEvent_t e2 = c->prof.get();
-            PSFM_HIP(hipEventRecord(e2, side));
-            pipe.ready_s2.push_back(e2);
-        }
+        if (p0 < n2 && (st = chunk(flows_f2, flows_b2, occ_s2, p0, n2 - p0 < pipe.chunk ? n2 - p0 : pipe.chunk, pipe.ready_s2)) != PSFM_OK) return st;
     }
     c->prof.end(side);
-    st = psfm_track_impl(c, flows_f, occ, flows_f2, occ_s2, n_flows, h, w, ratio, info, stream, &pipe, gate);
-    // psfm_track_impl synchronised `stream`, which waited on every chunk: the side stream is idle too
-    c->prof.pool.push_back(e_in);
-    for (auto e : pipe.ready) c->prof.pool.push_back(e);
-    for (auto e : pipe.ready_s2) c->prof.pool.push_back(e);
-    return st;
+    // psfm_track_impl synchronises `stream`, which waited on every chunk: the side stream is idle too when the pipeline's events go back
+    return psfm_track_impl(c, flows_f, occ, flows_f2, occ_s2, n_flows, h, w, ratio, info, stream, &pipe, gate);
 }
 
 extern "C" psfm_status psfm_result_device(psfm_ctx* c, const int32_t** birth, const int32_t** len, const int64_t** off,

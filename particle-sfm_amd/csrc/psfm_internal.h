@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 #include <shared_mutex>
 #include <string>
 #include <vector>
@@ -281,6 +282,76 @@ struct psfm_ctx {
 // solver's control block
 static inline PsfmShard* psfm_host_shards(const psfm_ctx* c) { return (PsfmShard*)((char*)c->host_pinned + 512); }
 static inline PsfmSolveCtrl* psfm_host_solve_ctrl(const psfm_ctx* c) { return (PsfmSolveCtrl*)(psfm_host_shards(c) + PSFM_NSHARD); }
+
+// What a call that runs the frame recurrence (psfm_track / psfm_connect, psfm_connect_batch per sequence) starts from: no solve
+// statistics, no result, no solves counted.  pc_persist_ok: the call has the device to itself (or a resident budget).
+static inline void psfm_call_begin(psfm_ctx* c, int n_flows, bool pc_persist_ok)
+{
+    c->solve_stats.clear();
+    c->res_n_traj = c->res_n_points = 0;
+    c->res_n_flows = n_flows;
+    c->res_is_query = false;
+    c->pc_persist_ok = pc_persist_ok;
+    c->pc_giveups = 0;
+    c->n_fused_ok = c->n_fused_redone = c->n_chain = 0;
+    c->n_resident = c->n_iter_launches = 0;
+}
+
+// ... and what it reports behind its finalize and the stream synchronisation (info may be NULL)
+static inline void psfm_fill_track_info(psfm_track_info* info, const psfm_ctx* c, int64_t cap, int64_t total_iters, int chain_mode)
+{
+    if (!info) return;
+    memset(info, 0, sizeof(*info));
+    info->n_traj = c->res_n_traj;
+    info->n_points = c->res_n_points;
+    info->n_lanes_peak = ((const PsfmCounters*)c->host_pinned)->n_lanes;
+    info->lane_capacity = cap;
+    info->solver_iterations = total_iters;
+    info->n_solves = (int32_t)c->solve_stats.size();
+    info->chain_mode = chain_mode;
+}
+
+// Occlusion maps produced on a side stream while the frame loop consumes them (psfm_connect, psfm_connect_batch): one event per
+// chunk of frame pairs; the loop waits for the chunk that contains the pair it is about to read.  The events come from the owner's
+// profiler pool and go back there when the call ends, however it ends (the stream is synchronised or the call failed; a recycled
+// event is re-recorded before anything waits on it).
+struct PsfmOccPipeline {
+    psfm_ctx* owner;
+    int chunk = 0;                       // frame pairs per chunk (0 = maps already complete)
+    hipEvent_t start = nullptr;          // what the side stream waits for: whatever the caller enqueued in front of the call
+    std::vector<hipEvent_t> ready;       // stride-1 maps: chunk c covers pairs [c*chunk, (c+1)*chunk)
+    std::vector<hipEvent_t> ready_s2;    // stride-2 maps
+    int waited = -1, waited_s2 = -1;
+    explicit PsfmOccPipeline(psfm_ctx* c) : owner(c) {}
+    PsfmOccPipeline(const PsfmOccPipeline&) = delete;
+    PsfmOccPipeline& operator=(const PsfmOccPipeline&) = delete;
+    ~PsfmOccPipeline()
+    {
+        if (start) owner->prof.pool.push_back(start);
+        for (auto e : ready) owner->prof.pool.push_back(e);
+        for (auto e : ready_s2) owner->prof.pool.push_back(e);
+    }
+    psfm_status need(int pair, bool s2, hipStream_t s)
+    {
+        if (chunk <= 0) return PSFM_OK;
+        std::vector<hipEvent_t>& ev = s2 ? ready_s2 : ready;
+        int& w = s2 ? waited_s2 : waited;
+        const int cidx = pair / chunk;
+        while (w < cidx && w + 1 < (int)ev.size()) {
+            ++w;
+            PSFM_HIP(hipStreamWaitEvent(s, ev[w], 0));
+        }
+        return PSFM_OK;
+    }
+};
+
+// The maps the path-consistency solve of frame f reads (positions at f-1, f, f+1): the stride-1 flows of f-1 and f, the stride-2
+// flow and occlusion map of f-1 (P = H W pixels per map)
+struct PsfmSolveMaps { const float* flow01; const float* flow12; const float* flow02; const uint8_t* occ02; };
+static inline PsfmSolveMaps psfm_solve_maps(const float* flows, const float* flows_f2, const uint8_t* occ_s2, int64_t P, int f)
+{
+    return {flows + (size_t)(f - 1) * P * 2, flows + (size_t)f * P * 2, flows_f2 + (size_t)(f - 1) * P * 2, occ_s2 + (size_t)(f - 1) * P};
+}
 
 // ---- launchers (psfm_track.hip) -------------------------------------------------------------
 psfm_status psfm_launch_flow_check(const float* ff, const float* fb, int n_pairs, int h, int w, float thres,

@@ -341,7 +341,7 @@ class HipShardEngine:
             seen.append(st)
             redo = fs
         if self._loc or self._peer:
-            # psfm_connect's rule (csrc/psfm_api.hip): a window with more than one solve in eight off the Gauss-Newton path sends the
+            # psfm_connect's rule (csrc/psfm_solve_policy.h: mode_next, unroll_next): a window with more than one solve in eight off the Gauss-Newton path sends the
             # next window to the resident solves, a clean one brings the fused solves back; launches per solve without a budget:
             # what the slowest solve of the window needed, within [4, 64]
             solved = [q for q in seen if q.termination >= 0]
@@ -359,6 +359,8 @@ class HipShardEngine:
 
     @staticmethod
     def _clean(st):
+        # psfm_solve_clean (csrc/psfm_solve_policy.h) WITHOUT its last clause, successful_steps + 1 <= kmax: a clean solve of more
+        # accepted steps than a fused launch holds counts as clean here, and _adapt caps what it asks for with K_MAX instead
         return st.dogleg_nonGN == 0 and st.termination != 5 and (st.iterations == st.successful_steps + 1 or
                                                                  (st.termination == 2 and st.iterations == st.successful_steps))
 
