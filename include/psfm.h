@@ -93,7 +93,8 @@ typedef struct psfm_track_info {
     int32_t chain_mode;        /* how the frame recurrence ran: 1 one launch per frame, 2 one persistent launch, 3 one launch per
                                   frame for a whole batch of sequences (psfm_connect_batch), 4 one launch per direction over
                                   caller-given query points (psfm_track_queries), 5 one loop of launches over frames for query points
-                                  with the path-consistency solve (psfm_track_queries_optimize) */
+                                  with the path-consistency solve (psfm_track_queries_optimize), 6 one launch per direction over the
+                                  query points of a whole batch of sequences (psfm_track_queries_batch) */
 } psfm_track_info;
 
 const char* psfm_last_error(void);
@@ -296,7 +297,8 @@ psfm_status psfm_connect(psfm_ctx* ctx, const float* flows_f, const float* flows
  * info->chain_mode = 4 -- and every consumer of a result works on it unchanged (psfm_result_device / _copy, psfm_result_filter /
  * _filtered_copy, psfm_window_sample, psfm_traj_to_matches, the label merge), except psfm_result_keys, whose key needs a birth grid
  * index: it refuses a query result (PSFM_ERR_ARG).  Identical calls give identical bytes.  Synchronises `stream`.
- * Out of scope: tracking through occlusion, several sequences per call.  (Path consistency: psfm_track_queries_optimize.) */
+ * Out of scope: tracking through occlusion.  (Path consistency: psfm_track_queries_optimize; several sequences per call:
+ * psfm_track_queries_batch.) */
 psfm_status psfm_track_queries(psfm_ctx* ctx, const float* flows_f, const uint8_t* occ_f, const float* flows_b, const uint8_t* occ_b,
                                int n_flows, int h, int w, const double* q_xy, const int32_t* q_t, int64_t n_q,
                                psfm_track_info* info_host, void* stream);
@@ -333,6 +335,41 @@ psfm_status psfm_track_queries_optimize(psfm_ctx* ctx, const float* flows_f, con
                                         const uint8_t* occ_f2, const float* flows_b, const uint8_t* occ_b, const float* flows_b2,
                                         const uint8_t* occ_b2, int n_flows, int h, int w, const double* q_xy, const int32_t* q_t,
                                         int64_t n_q, psfm_track_info* info_host, void* stream);
+
+/* psfm_track_queries for n_seq sequences in ONE call: sequence i -- its stacks, its frame size h[i] x w[i], its n_flows[i] maps, its
+ * n_q[i] queries -- is tracked into ctxs[i], and there is NO new rule: afterwards context i holds byte for byte what
+ * psfm_track_queries(ctxs[i], ... sequence i ...) would have left (birth, len, off, xy, the sizes; the result is marked as a query
+ * result, so psfm_result_keys refuses it; a live label merge is void; the solve statistics are cleared and an unfinished sharded run
+ * is abandoned), and every consumer runs unchanged, context by context (psfm_result_*, psfm_result_filter(_batch),
+ * psfm_window_sample(_batch), psfm_traj_to_matches(_batch), the label merge).  infos_host[i].chain_mode = 6.
+ *   ctxs[i]      one context per sequence, 1 <= n_seq <= 64, distinct, non-NULL, all on one device; ctxs[0] also owns the call's
+ *                shared workspace
+ *   flows_f, occ_f   both NULL, or both arrays of n_seq non-NULL pointers: a direction is given for the WHOLE batch.  The same for
+ *                flows_b, occ_b (flows_b[i][f]: frame f+1 -> f, with ITS maps).  At least one direction
+ *   n_flows[i] >= 1, h[i], w[i]   may differ from sequence to sequence
+ *   q_xy[i] (n_q[i],2) f64, q_t[i] (n_q[i]) i32   on the DEVICE; n_q[i] == 0 is legal (that context gets the empty result, the others
+ *                go on); all sequences together have fewer than 2^28 queries
+ *   infos_host   n_seq entries or NULL
+ * Motion boundary (psfm_ctx_set_motion_boundary): on in EVERY context of the batch, each with its own threshold, or in none.  With it
+ * on the kill maps of each stack being sampled are built from that stack's own flows and maps into its context, one launch per stack,
+ * before the tracking launch.
+ * Refused with PSFM_ERR_ARG, BEFORE anything is tracked and with EVERY context untouched: n_seq out of range; a NULL, repeated or
+ * foreign-device context; no direction, or a stack without its maps; a NULL entry in a given array; n_flows[i] < 1 or a bad frame
+ * size; n_q[i] < 0, or n_q[i] > 0 with a NULL q_xy[i] or q_t[i]; 2^28 or more queries; contexts that disagree about the motion
+ * boundary; a query with a non-finite coordinate or a frame outside [0, n_flows[i]] -- psfm_last_error() names the lowest such
+ * sequence and the lowest such query inside it.
+ * Three host synchronisations, as the single call: behind the validation, behind the per-sequence point totals, at the end (a batch
+ * without any query has nothing to validate or track: two synchronisations around the table's copy, one launch for the empty results and the totals' copy).  Apart
+ * from the kill maps the number of launches and copies does not depend on n_seq; psfm_query_batch_census reports both figures for
+ * the last call that had `ctx` as ctxs[0] (the kill maps' launches are not counted).  Integer sums in a fixed order: identical calls
+ * give identical bytes.  Synchronises `stream`.
+ * Out of scope: path consistency for a batch of sequences (psfm_track_queries_optimize solves jointly per sequence, with a host
+ * decision per frame). */
+psfm_status psfm_track_queries_batch(psfm_ctx* const* ctxs, int n_seq, const float* const* flows_f, const uint8_t* const* occ_f,
+                                     const float* const* flows_b, const uint8_t* const* occ_b, const int* n_flows, const int* h,
+                                     const int* w, const double* const* q_xy, const int32_t* const* q_t, const int64_t* n_q,
+                                     psfm_track_info* infos_host, void* stream);
+psfm_status psfm_query_batch_census(psfm_ctx* ctx, int32_t* launches, int32_t* host_syncs);
 
 /* The loop of the reference's driver over a directory of sequences (run_particlesfm.py:168-176 -> connect_point_trajectory ->
  * main_connect_point_trajectories.py:36-53 per sequence) for n_seq sequences of the SAME frame size and sample ratio (any
@@ -532,8 +569,8 @@ psfm_status psfm_traj_decode_batch(psfm_ctx* ctx, int n_win, const float* const*
  *            the plan call, or one ordered behind it): no synchronisation, no allocation.  capacity below the sum of k:
  *            PSFM_ERR_CAPACITY, nothing written.
  *            Without a matching plan the call makes the plan itself (one synchronisation), then gathers.  A stale plan is never
- *            used: psfm_track, psfm_connect, psfm_connect_batch, psfm_track_queries, psfm_track_queries_optimize and
- *            psfm_result_filter on the context void it, as does any differing argument.
+ *            used: psfm_track, psfm_connect, psfm_connect_batch, psfm_track_queries, psfm_track_queries_optimize,
+ *            psfm_track_queries_batch and psfm_result_filter on the context void it, as does any differing argument.
  *   PSFM_ERR_ARG: n_win outside [0, 64], n_frames < 1, max_num_tracks < 0, capacity < 0, a NULL host array with n_win > 0, sizes < 1
  *   with xy_norm given, a window whose frame0 + n_frames leaves the 32-bit range.
  *

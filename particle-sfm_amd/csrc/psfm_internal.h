@@ -177,6 +177,12 @@ struct psfm_ctx {
                                    // refuses it); cleared by every other entry point that replaces the result
     PsfmBuf qr_ws;                 // psfm_track_queries (psfm_query.hip): first refused query | lengths per direction | scan storage
                                    // (psfm_track_queries_optimize, psfm_query_pc.hip: ... | rows per wave | the rows of a frame's solve)
+    // psfm_track_queries_batch (psfm_query_batch.hip), this context as the call's owner: the table of sequences | the block prefix |
+    // the refusal slots; lengths per direction of all sequences | scan storage | point totals; their pinned staging; the census of
+    // the last call (psfm_query_batch_census)
+    PsfmBuf qb_tab, qb_ws;
+    void* qb_host = nullptr;
+    int32_t qb_launches = 0, qb_syncs = 0;
     // solver workspace
     PsfmBuf sol_x, sol_state, sol_partials, sol_ctrl, sol_misc, sol_stats, sol_fused, sol_bar;
     PsfmBuf sol_list;              // launch chain / resident solve: per block, the lanes that take part in the solve (pc_build_list)

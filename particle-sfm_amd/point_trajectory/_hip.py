@@ -39,6 +39,7 @@ EXPORTS = [
     "psfm_depth_display", "psfm_ctx_set_depth_display", "psfm_depth_display_last_ms", "psfm_depth_display_chunk",
     "psfm_track_queries", "psfm_track_queries_optimize",
     "psfm_result_filter_batch", "psfm_traj_to_matches_batch", "psfm_labels_to_matches_batch", "psfm_matches_batch_census", "psfm_labels_sizes",
+    "psfm_track_queries_batch", "psfm_query_batch_census",
 ]
 
 
@@ -105,6 +106,10 @@ def lib():
                                      ctypes.POINTER(i32), i32, i32, f32, i32, ctypes.POINTER(TrackInfo), vp]
     L.psfm_track_queries.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, i64, ctypes.POINTER(TrackInfo), vp]
     L.psfm_track_queries_optimize.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, i64, ctypes.POINTER(TrackInfo), vp]
+    L.psfm_track_queries_batch.argtypes = [ctypes.POINTER(vp), i32, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp),
+                                           ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(vp), ctypes.POINTER(vp),
+                                           ctypes.POINTER(i64), ctypes.POINTER(TrackInfo), vp]
+    L.psfm_query_batch_census.argtypes = [vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]
     L.psfm_result_device.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp)]
     L.psfm_result_copy.argtypes = [vp, vp, vp, vp, vp, vp]
     L.psfm_result_solve_stats.argtypes = [vp, ctypes.POINTER(SolveStats), i32, ctypes.POINTER(ctypes.c_int32)]
@@ -276,6 +281,13 @@ class Context:
         a = ctypes.c_int32()
         check(lib().psfm_ctx_get_finalize_placed(self._h, ctypes.byref(a)))
         return int(a.value)
+
+    def query_batch_census(self):
+        """Launches (kernels and copies, the kill maps of the motion-boundary option apart) and host synchronisations of the last
+        psfm_track_queries_batch call that had this context as its first."""
+        a, b = ctypes.c_int32(), ctypes.c_int32()
+        check(lib().psfm_query_batch_census(self._h, ctypes.byref(a), ctypes.byref(b)))
+        return {"launches": int(a.value), "host_syncs": int(b.value)}
 
     def set_sparse_depth(self, budget_bytes=1 << 30, timing=False):
         """psfm_sfm.convert: bytes of depth maps + winner maps (12 per pixel) one psfm_sparse_depth call may take (0: no limit; one

@@ -588,3 +588,141 @@ def run_connect_queries(xy, t, flows_f, flows_b, thres=1.0, direction="forward",
         if f2 is not None:
             kw.update(flows_b2=b2, occ_b2=flow_check_device(b2, f2, thres)[1] if n > 1 else f2.new_zeros((0,) + tuple(ff.shape[1:3]), dtype=torch.uint8))
     return run_track_queries(xy, t, motion_boundary=motion_boundary, mb_thres=mb_thres, return_device=return_device, **kw)
+
+
+QUERY_BATCH_MAX_SEQ = 64             # PSFM_BATCH_MAX
+QUERY_BATCH_MAX_QUERIES = 1 << 28    # queries of one psfm_track_queries_batch call: fewer than this
+
+
+def _query_batch_groups(n_q):
+    """Consecutive groups of at most 64 sequences and fewer than 2^28 queries: [(start, end)].  (A single sequence at or above the
+    bound forms a group of its own, which the library refuses as it refuses it in psfm_track_queries.)"""
+    groups, start, total = [], 0, 0
+    for i, n in enumerate(n_q):
+        if i > start and (i - start >= QUERY_BATCH_MAX_SEQ or total + n >= QUERY_BATCH_MAX_QUERIES):
+            groups.append((start, i))
+            start, total = i, 0
+        total += n
+    if len(n_q) > start:
+        groups.append((start, len(n_q)))
+    return groups
+
+
+def run_track_queries_batch(seqs, motion_boundary=False, mb_thres=0.02, return_device=False):
+    """run_track_queries for a LIST of sequences in one psfm_track_queries_batch call per group of at most 64 sequences (and fewer
+    than 2^28 queries): every launch covers the queries of the whole group, so a directory of small videos pays the fixed cost of a
+    call once.  seqs: dicts with `xy` ((Q,2) float64), `t` ((Q,) int) and the stacks of run_track_queries -- `flows`, `occ` (forward)
+    and / or `flows_b`, `occ_b` (backward) -- each sequence with its own frame size, length and query count (zero queries: the empty
+    result).  Every sequence must give the same direction(s): a ValueError otherwise.  Sequence i's result is byte for byte that of
+    run_track_queries on it alone; R.info["chain_mode"] is 6.
+    motion_boundary / mb_thres: as in run_connect_batch -- one threshold, or one per sequence; the option is set on the batch contexts
+    (_hip.batch_contexts) for the duration of the call.
+    Returns one TrajectoryList per sequence; with return_device=True (contexts, infos) -- context i holds sequence i's result until
+    the calling thread's next batch -- which needs the list to fit one group.
+    The stride-2 path-consistency form is out of scope (psfm_track_queries_optimize solves jointly per sequence with a host decision
+    per frame): a sequence that comes with flows_f2 / occ_f2 / flows_b2 / occ_b2 is a ValueError; use run_track_queries for it."""
+    import torch
+    n_seq = len(seqs)
+    if n_seq < 1:
+        return ([], []) if return_device else []
+    mb_list = None
+    if motion_boundary:
+        mb_list = [float(mb_thres)] * n_seq if np.isscalar(mb_thres) else [float(v) for v in mb_thres]
+        if len(mb_list) != n_seq:
+            raise ValueError("track_queries_batch: %d thresholds for %d sequences" % (len(mb_list), n_seq))
+    first = _hip.context()
+    dev = torch.device("cuda", first.device)
+
+    def as_t(a, dt):
+        a = a.detach() if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
+        return a.to(device=dev, dtype=dt)
+    prepared, dirs0 = [], None
+    for i, sq in enumerate(seqs):
+        if any(sq.get(k) is not None for k in ("flows_f2", "occ_f2", "flows_b2", "occ_b2")):
+            raise ValueError("track_queries_batch: sequence %d comes with stride-2 stacks; path consistency for a batch of sequences "
+                             "is out of scope, use run_track_queries for it" % i)
+        m = {}
+        for name, dt, tail in (("flows", torch.float32, (1, 1, 2)), ("occ", torch.uint8, (1, 1)), ("flows_b", torch.float32, (1, 1, 2)),
+                               ("occ_b", torch.uint8, (1, 1))):
+            m[name] = _as_device_stack(sq[name], dt, tail) if sq.get(name) is not None else None
+        if (m["flows"] is None) != (m["occ"] is None) or (m["flows_b"] is None) != (m["occ_b"] is None) or (m["flows"] is None and m["flows_b"] is None):
+            raise ValueError("track_queries_batch: sequence %d: give at least one stack, and every stack with its occlusion maps" % i)
+        dirs = (m["flows"] is not None, m["flows_b"] is not None)
+        if dirs0 is None:
+            dirs0 = dirs
+        elif dirs != dirs0:
+            raise ValueError("track_queries_batch: sequence %d gives other directions than sequence 0 (a direction is given for the whole batch)" % i)
+        ref = m["flows"] if m["flows"] is not None else m["flows_b"]
+        n, H, W = int(ref.shape[0]), int(ref.shape[1]), int(ref.shape[2])
+        for name, tail in (("flows", (H, W, 2)), ("occ", (H, W)), ("flows_b", (H, W, 2)), ("occ_b", (H, W))):
+            if m[name] is not None and (int(m[name].shape[0]) != n or tuple(m[name].shape[1:]) != tail):
+                raise ValueError("track_queries_batch: sequence %d: %s has shape %s, expected %s" % (i, name, tuple(m[name].shape), (n,) + tail))
+        q_xy = as_t(sq["xy"], torch.float64).reshape(-1, 2).contiguous()
+        q_t = as_t(sq["t"], torch.int32).reshape(-1).contiguous()
+        if q_t.shape[0] != q_xy.shape[0]:
+            raise ValueError("track_queries_batch: sequence %d: %d positions for %d frames" % (i, q_xy.shape[0], q_t.shape[0]))
+        prepared.append((m, n, H, W, q_xy, q_t))
+    groups = _query_batch_groups([int(p[4].shape[0]) for p in prepared])
+    if return_device and len(groups) > 1:
+        raise ValueError("track_queries_batch: return_device needs at most %d sequences and fewer than 2^28 queries (one call)" % QUERY_BATCH_MAX_SEQ)
+    vp = ctypes.c_void_p
+    results = []
+    for g0, g1 in groups:
+        B = g1 - g0
+        ctxs = _hip.batch_contexts(B)
+        handles = (vp * B)(*[c.handle for c in ctxs])
+        ff, of, fb, ob, qx, qt = ((vp * B)() for _ in range(6))
+        nf, hh, ww, nq = (ctypes.c_int * B)(), (ctypes.c_int * B)(), (ctypes.c_int * B)(), (ctypes.c_int64 * B)()
+        for k, (m, n, H, W, q_xy, q_t) in enumerate(prepared[g0:g1]):
+            if dirs0[0]:
+                ff[k], of[k] = m["flows"].data_ptr(), m["occ"].data_ptr()
+            if dirs0[1]:
+                fb[k], ob[k] = m["flows_b"].data_ptr(), m["occ_b"].data_ptr()
+            nf[k], hh[k], ww[k], nq[k] = n, H, W, int(q_xy.shape[0])
+            if nq[k] > 0:
+                qx[k], qt[k] = q_xy.data_ptr(), q_t.data_ptr()
+        infos = (_hip.TrackInfo * B)()
+        try:
+            if mb_list is not None:
+                for c, v in zip(ctxs, mb_list[g0:g1]):
+                    c.set_motion_boundary(True, v)
+            st = _hip.lib().psfm_track_queries_batch(handles, B, ff if dirs0[0] else None, of if dirs0[0] else None, fb if dirs0[1] else None,
+                                                     ob if dirs0[1] else None, nf, hh, ww, qx, qt, nq, infos,
+                                                     _hip.current_stream_ptr(ctxs[0].device))
+        finally:
+            if mb_list is not None:      # (the option is per context and the thread's batch contexts are reused: off again, whatever happened)
+                for c in ctxs:
+                    c.set_motion_boundary(False)
+        _hip.check(st)
+        if return_device:
+            return ctxs, [infos[k] for k in range(B)]
+        results.extend(_result_to_host(c, infos[k]) for k, c in enumerate(ctxs))
+    return results
+
+
+def run_connect_queries_batch(seqs, thres=1.0, direction="forward", motion_boundary=False, mb_thres=0.02, return_device=False):
+    """flow_check + run_track_queries_batch: seqs are dicts with `xy`, `t`, `flows_f` and `flows_b` ((n,H,W,2), flows_b[f]: frame f+1
+    -> f); the occlusion maps each direction needs come from flow_check_device in that direction's own orientation, as in
+    run_connect_queries -- forward: flow_check(flows_f, flows_b); backward: flow_check(flows_b, flows_f).  direction: "forward",
+    "backward" or "both", for the whole batch.  Path consistency for a batch of sequences is out of scope: a sequence that comes with
+    flows_f2 / flows_b2 is a ValueError; use run_connect_queries for it."""
+    import torch
+    from .utils import flow_check_device
+    if direction not in ("forward", "backward", "both"):
+        raise ValueError("connect_queries_batch: direction must be 'forward', 'backward' or 'both'")
+    out = []
+    for i, sq in enumerate(seqs):
+        if sq.get("flows_f2") is not None or sq.get("flows_b2") is not None:
+            raise ValueError("connect_queries_batch: sequence %d comes with stride-2 stacks; path consistency for a batch of sequences "
+                             "is out of scope, use run_connect_queries (run_track_queries) for it" % i)
+        ff = _as_device_stack(sq["flows_f"], torch.float32, (1, 1, 2))
+        fb = _as_device_stack(sq["flows_b"], torch.float32, (1, 1, 2))
+        n = min(int(ff.shape[0]), int(fb.shape[0]))
+        ff, fb = ff[:n], fb[:n]
+        kw = dict(xy=sq["xy"], t=sq["t"])
+        if direction in ("forward", "both"):
+            kw.update(flows=ff, occ=flow_check_device(ff, fb, thres)[1])
+        if direction in ("backward", "both"):
+            kw.update(flows_b=fb, occ_b=flow_check_device(fb, ff, thres)[1])
+        out.append(kw)
+    return run_track_queries_batch(out, motion_boundary=motion_boundary, mb_thres=mb_thres, return_device=return_device)
