@@ -94,7 +94,9 @@ typedef struct psfm_track_info {
                                   frame for a whole batch of sequences (psfm_connect_batch), 4 one launch per direction over
                                   caller-given query points (psfm_track_queries), 5 one loop of launches over frames for query points
                                   with the path-consistency solve (psfm_track_queries_optimize), 6 one launch per direction over the
-                                  query points of a whole batch of sequences (psfm_track_queries_batch) */
+                                  query points of a whole batch of sequences (psfm_track_queries_batch), 7 one loop of launches over
+                                  the steps of a whole batch of sequences with the multi-problem path-consistency solve
+                                  (psfm_track_queries_optimize_batch) */
 } psfm_track_info;
 
 const char* psfm_last_error(void);
@@ -363,13 +365,48 @@ psfm_status psfm_track_queries_optimize(psfm_ctx* ctx, const float* flows_f, con
  * from the kill maps the number of launches and copies does not depend on n_seq; psfm_query_batch_census reports both figures for
  * the last call that had `ctx` as ctxs[0] (the kill maps' launches are not counted).  Integer sums in a fixed order: identical calls
  * give identical bytes.  Synchronises `stream`.
- * Out of scope: path consistency for a batch of sequences (psfm_track_queries_optimize solves jointly per sequence, with a host
- * decision per frame). */
+ * (Path consistency for a batch of sequences: psfm_track_queries_optimize_batch.) */
 psfm_status psfm_track_queries_batch(psfm_ctx* const* ctxs, int n_seq, const float* const* flows_f, const uint8_t* const* occ_f,
                                      const float* const* flows_b, const uint8_t* const* occ_b, const int* n_flows, const int* h,
                                      const int* w, const double* const* q_xy, const int32_t* const* q_t, const int64_t* n_q,
                                      psfm_track_info* infos_host, void* stream);
 psfm_status psfm_query_batch_census(psfm_ctx* ctx, int32_t* launches, int32_t* host_syncs);
+
+/* psfm_track_queries_optimize for n_seq sequences in ONE call: the query points of every sequence tracked with the stride-2
+ * path-consistency solve after every step (track_optimize.py:49-50), with one set of launches per step for the whole batch.  The
+ * arguments are psfm_track_queries_batch's plus the four stride-2 arrays:
+ *   flows_f2[i] (n_flows[i]-1,H_i,W_i,2), occ_f2[i] (n_flows[i]-1,H_i,W_i)   with the forward direction
+ *   flows_b2[i], occ_b2[i]                                                   with the backward direction (flows_b2[i][f]: frame f+2 -> f)
+ * each an array of n_seq pointers or NULL for the whole batch, as the stride-1 arrays are; a sequence with n_flows[i] == 1 may have
+ * NULL entries (no solve can happen in it).  Up to 64 sequences, each with its own frame size, length and query count (zero
+ * included); one context per sequence, ctxs[0] owns the batch's shared workspace; the gate and the motion-boundary rule (on every
+ * context or on none, each with its own threshold, one kill-map launch per stack) are psfm_track_queries_batch's.
+ * Per direction and step k = 0 .. max(n_flows) - 1: one step launch over all sequences (the per-lane step of
+ * psfm_track_queries_optimize; a sequence with n_flows[i] <= k does nothing), and from k = 1 on one scan launch (one block per
+ * sequence) that leaves every sequence's row count in device memory, one rows launch that writes the solves' inputs in place, the
+ * launch chain of the solver over the table of all sequences' problems -- iteration 0 and the trust-region iterations as one grid
+ * (blocks, problems) per launch, a problem's block count computed on the device from its row count, every sum in the single solve's
+ * order --, one poll (a small launch that packs every control block into pinned memory) with ONE synchronisation, further chunks of
+ * iteration launches while any problem is left undone, then the write-back and the scatter.  The host never reads a row count.  At
+ * the end one length scan and one CSR gather for all contexts.
+ * Context i ends up with what psfm_track_queries_optimize(ctxs[i], ... sequence i ...) leaves: the result set (trajectory q is query
+ * q, psfm_result_keys refuses it) and psfm_result_solve_stats -- one entry per solve that had rows, forward frames ascending, then
+ * backward frames in the order they ran; the solves run as launches (no resident form), whose iterates are the resident form's bit
+ * for bit.  infos_host[i].chain_mode = 7; n_solves and solver_iterations are sequence i's.
+ * Refusals (PSFM_ERR_ARG before anything is tracked, every context untouched): those of psfm_track_queries_batch -- the lowest bad
+ * sequence and its lowest bad query are named -- and those of psfm_track_queries_optimize: a stride-2 array without its occlusion
+ * array or without the direction's stride-1 arrays; a sequence whose stride-2 stack comes without its maps; a direction whose
+ * stride-1 stack lacks its stride-2 stack in a sequence with n_flows >= 2 (the sequence is named).
+ * psfm_query_pc_batch_census: the last call that had `ctx` as ctxs[0] -- launches_fixed (kernels and copies that do not depend on
+ * how the solves went nor on n_seq; the kill maps apart), launches_iter (trust-region iteration launches, each over all problems),
+ * host_syncs (validation, one per poll, the point totals, the end).  Identical calls give identical bytes.  Synchronises `stream`.
+ * Out of scope: the resident and fused solver forms for a batch; a device-paced frame loop (one synchronisation per step remains). */
+psfm_status psfm_track_queries_optimize_batch(psfm_ctx* const* ctxs, int n_seq, const float* const* flows_f, const uint8_t* const* occ_f,
+                                              const float* const* flows_f2, const uint8_t* const* occ_f2, const float* const* flows_b,
+                                              const uint8_t* const* occ_b, const float* const* flows_b2, const uint8_t* const* occ_b2,
+                                              const int* n_flows, const int* h, const int* w, const double* const* q_xy,
+                                              const int32_t* const* q_t, const int64_t* n_q, psfm_track_info* infos_host, void* stream);
+psfm_status psfm_query_pc_batch_census(psfm_ctx* ctx, int32_t* launches_fixed, int32_t* launches_iter, int32_t* host_syncs);
 
 /* The loop of the reference's driver over a directory of sequences (run_particlesfm.py:168-176 -> connect_point_trajectory ->
  * main_connect_point_trajectories.py:36-53 per sequence) for n_seq sequences of the SAME frame size and sample ratio (any

@@ -183,6 +183,12 @@ struct psfm_ctx {
     PsfmBuf qb_tab, qb_ws;
     void* qb_host = nullptr;
     int32_t qb_launches = 0, qb_syncs = 0;
+    // psfm_track_queries_optimize_batch (psfm_query_pc_batch.hip), this context as the call's owner: the tables of the frame loop and of
+    // the multi-problem solves | rows per wave of all sequences, row counts; the pinned staging of the tables and of the poll; the
+    // census of the last call (psfm_query_pc_batch_census).  Every context of a call: the owner (query) of every row of its solve
+    PsfmBuf qpb_tab, qpb_ws, qpb_owner;
+    void* qpb_host = nullptr;
+    int32_t qpb_fixed = 0, qpb_iter = 0, qpb_syncs = 0;
     // solver workspace
     PsfmBuf sol_x, sol_state, sol_partials, sol_ctrl, sol_misc, sol_stats, sol_fused, sol_bar;
     PsfmBuf sol_list;              // launch chain / resident solve: per block, the lanes that take part in the solve (pc_build_list)
@@ -402,6 +408,30 @@ psfm_status psfm_query_refuse(psfm_ctx* c, const char* who, const double* q_xy, 
 // births, lengths, offsets and the CSR of Q > 0 queries from the position slab in c->log and the directions' lengths (NULL: not tracked)
 psfm_status psfm_query_finish(psfm_ctx* c, const int32_t* q_t, const int* len_f, const int* len_b, unsigned Q, int n_flows, int64_t* bsum,
                               int64_t* n_points, hipStream_t s);
+
+// ---- psfm_track_queries_batch (psfm_query_batch.hip) as a frame: psfm_qb_run with hooks == NULL is that call; with hooks it is the
+// staging, the refusals, the contexts' bookkeeping, the length scan and the CSR gather around ANOTHER tracking loop
+// (psfm_track_queries_optimize_batch, psfm_query_pc_batch.hip) ----
+struct PsfmQbSeq;         // psfm_query_batch.h
+struct PsfmQbRun {
+    psfm_ctx* own; psfm_ctx* const* ctxs; int n_seq;
+    const PsfmQbSeq* tab_host;                  // the table as it was uploaded (masks: the kill maps under the motion-boundary option)
+    const PsfmQbSeq* tab; const int* blk_end;   // ... and on the device, with the inclusive block prefix
+    int blocks;                                 // of the flattened grids (> 0)
+    bool mb;
+    hipStream_t s;
+};
+struct PsfmQbHooks {
+    const char* who;                                            // the entry point's name, for the refusals
+    int chain_mode;                                             // what psfm_track_info::chain_mode reports
+    psfm_status (*check)(void* user, int seq);                  // further argument checks: seq == -1 once in front, then per sequence
+    psfm_status (*track)(void* user, const PsfmQbRun& run);     // the tracking: leaves every slab and the lengths per direction
+    void* user;
+};
+psfm_status psfm_qb_run(psfm_ctx* const* ctxs, int n_seq, const float* const* flows_f, const uint8_t* const* occ_f,
+                        const float* const* flows_b, const uint8_t* const* occ_b, const int* n_flows, const int* h, const int* w,
+                        const double* const* q_xy, const int32_t* const* q_t, const int64_t* n_q, psfm_track_info* infos_host, void* stream,
+                        const PsfmQbHooks* hooks);
 
 // ---- batch: B same-shape sequences per launch (psfm_batch.hip; kernels beside their single-sequence forms) --------------------
 #define PSFM_BATCH_MAX 64

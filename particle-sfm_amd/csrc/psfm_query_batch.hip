@@ -200,7 +200,6 @@ struct QbStaging {
 };
 }  // namespace
 
-#define QB_WHO "psfm_track_queries_batch"
 #define QB_LAUNCH(kernel, grid, ...)                                                                     \
     do {                                                                                                 \
         hipLaunchKernelGGL(kernel, dim3((unsigned)(grid)), dim3(QB_BLOCK), 0, s, __VA_ARGS__);           \
@@ -216,52 +215,60 @@ static void qb_launch_track(psfm_ctx* own, const PsfmQbSeq* tab, const int* blk_
     else QB_LAUNCH((psfm_query_batch_track_kernel<false, BACK>), blocks, tab, blk_end);
 }
 
-extern "C" psfm_status psfm_track_queries_batch(psfm_ctx* const* ctxs, int n_seq, const float* const* flows_f, const uint8_t* const* occ_f,
-                                                const float* const* flows_b, const uint8_t* const* occ_b, const int* n_flows, const int* h,
-                                                const int* w, const double* const* q_xy, const int32_t* const* q_t, const int64_t* n_q,
-                                                psfm_track_info* infos_host, void* stream)
+// The call.  hooks == NULL: psfm_track_queries_batch.  With hooks (psfm_track_queries_optimize_batch, psfm_query_pc_batch.hip) the
+// arguments are checked further, sequence by sequence in the same pass, and the caller's frame loop runs in place of the two tracking
+// launches; everything around them -- staging, refusals, what happens to the contexts, the one length scan and the one CSR gather
+// for all contexts -- is this function's.
+psfm_status psfm_qb_run(psfm_ctx* const* ctxs, int n_seq, const float* const* flows_f, const uint8_t* const* occ_f,
+                        const float* const* flows_b, const uint8_t* const* occ_b, const int* n_flows, const int* h, const int* w,
+                        const double* const* q_xy, const int32_t* const* q_t, const int64_t* n_q, psfm_track_info* infos_host, void* stream,
+                        const PsfmQbHooks* hooks)
 {
+    const char* who = hooks ? hooks->who : "psfm_track_queries_batch";
     // ---- arguments: before any allocation or launch ----
     if (!ctxs || n_seq < 1 || n_seq > PSFM_BATCH_MAX) {
-        psfm_set_error(QB_WHO ": bad argument (n_seq=%d of 1..%d)", n_seq, PSFM_BATCH_MAX);
+        psfm_set_error("%s: bad argument (n_seq=%d of 1..%d)", who, n_seq, PSFM_BATCH_MAX);
         return PSFM_ERR_ARG;
     }
     for (int i = 0; i < n_seq; ++i) {
         if (!ctxs[i] || !ctxs[0] || ctxs[i]->device != ctxs[0]->device) {
-            psfm_set_error(QB_WHO ": context %d is NULL or on another device", i);
+            psfm_set_error("%s: context %d is NULL or on another device", who, i);
             return PSFM_ERR_ARG;
         }
         for (int j = 0; j < i; ++j)
-            if (ctxs[j] == ctxs[i]) { psfm_set_error(QB_WHO ": context %d given twice (one per sequence)", i); return PSFM_ERR_ARG; }
+            if (ctxs[j] == ctxs[i]) { psfm_set_error("%s: context %d given twice (one per sequence)", who, i); return PSFM_ERR_ARG; }
     }
     if ((!flows_f && !flows_b) || (flows_f != nullptr) != (occ_f != nullptr) || (flows_b != nullptr) != (occ_b != nullptr)) {
-        psfm_set_error(QB_WHO ": give at least one stack per sequence, and every stack with its occlusion maps");
+        psfm_set_error("%s: give at least one stack per sequence, and every stack with its occlusion maps", who);
         return PSFM_ERR_ARG;
     }
-    if (!n_flows || !h || !w || !n_q) { psfm_set_error(QB_WHO ": NULL argument (n_flows, h, w, n_q: one entry per sequence)"); return PSFM_ERR_ARG; }
+    psfm_status st;
+    if (hooks && (st = hooks->check(hooks->user, -1)) != PSFM_OK) return st;
+    if (!n_flows || !h || !w || !n_q) { psfm_set_error("%s: NULL argument (n_flows, h, w, n_q: one entry per sequence)", who); return PSFM_ERR_ARG; }
     int64_t nq[PSFM_QB_MAX], N = 0;
     for (int i = 0; i < n_seq; ++i) {
         if ((flows_f && (!flows_f[i] || !occ_f[i])) || (flows_b && (!flows_b[i] || !occ_b[i]))) {
-            psfm_set_error(QB_WHO ": sequence %d: a stack or its occlusion maps are NULL (a direction is given for the whole batch)", i);
+            psfm_set_error("%s: sequence %d: a stack or its occlusion maps are NULL (a direction is given for the whole batch)", who, i);
             return PSFM_ERR_ARG;
         }
         if (n_flows[i] < 1 || !psfm_frame_ok(h[i], w[i])) {
-            psfm_set_error(QB_WHO ": sequence %d: bad argument (n_flows=%d h=%d w=%d)", i, n_flows[i], h[i], w[i]);
+            psfm_set_error("%s: sequence %d: bad argument (n_flows=%d h=%d w=%d)", who, i, n_flows[i], h[i], w[i]);
             return PSFM_ERR_ARG;
         }
         if (n_q[i] < 0 || (n_q[i] > 0 && (!q_xy || !q_t || !q_xy[i] || !q_t[i]))) {
-            psfm_set_error(QB_WHO ": sequence %d: bad argument (n_q=%lld: n_q >= 0, q_xy and q_t on the device)", i, (long long)n_q[i]);
+            psfm_set_error("%s: sequence %d: bad argument (n_q=%lld: n_q >= 0, q_xy and q_t on the device)", who, i, (long long)n_q[i]);
             return PSFM_ERR_ARG;
         }
         // the 32-bit lane offset of a slab row (16 bytes per query) and the block count of the flattened grid
         if (n_q[i] >= ((int64_t)1 << 28) || (N += n_q[i]) >= ((int64_t)1 << 28)) {
-            psfm_set_error(QB_WHO ": sequence %d: 2^28 or more queries in the batch", i);
+            psfm_set_error("%s: sequence %d: 2^28 or more queries in the batch", who, i);
             return PSFM_ERR_ARG;
         }
         nq[i] = n_q[i];
+        if (hooks && (st = hooks->check(hooks->user, i)) != PSFM_OK) return st;
         if (ctxs[i]->mb_enable != ctxs[0]->mb_enable) {      // (one kernel form per launch: all sequences with the second verdict, or none)
-            psfm_set_error(QB_WHO ": context %d has the motion-boundary option %s, context 0 has it %s: it must be "
-                           "on every context or on none (each with its own threshold)", i, ctxs[i]->mb_enable ? "on" : "off",
+            psfm_set_error("%s: context %d has the motion-boundary option %s, context 0 has it %s: it must be "
+                           "on every context or on none (each with its own threshold)", who, i, ctxs[i]->mb_enable ? "on" : "off",
                            ctxs[0]->mb_enable ? "on" : "off");
             return PSFM_ERR_ARG;
         }
@@ -270,7 +277,6 @@ extern "C" psfm_status psfm_track_queries_batch(psfm_ctx* const* ctxs, int n_seq
     PSFM_HIP(hipSetDevice(own->device));
     PsfmGate gate(own->device, 0);
     hipStream_t s = (hipStream_t)stream;
-    psfm_status st;
     own->qb_launches = own->qb_syncs = 0;
     const bool mb = own->mb_enable;
 
@@ -311,7 +317,7 @@ extern "C" psfm_status psfm_track_queries_batch(psfm_ctx* const* ctxs, int n_seq
         QB_SYNC();
         for (int i = 0; i < n_seq; ++i)
             if (hs->bad[i] != ~0ull) {
-                psfm_set_error(QB_WHO ": sequence %d: query %llu has a non-finite coordinate or a frame outside [0, %d]", i, hs->bad[i],
+                psfm_set_error("%s: sequence %d: query %llu has a non-finite coordinate or a frame outside [0, %d]", who, i, hs->bad[i],
                                n_flows[i]);
                 return PSFM_ERR_ARG;
             }
@@ -359,8 +365,15 @@ extern "C" psfm_status psfm_track_queries_batch(psfm_ctx* const* ctxs, int n_seq
     QB_COPY(du, &hs->up, sizeof(QbUpload), hipMemcpyHostToDevice);
     if (blocks > 0) {
         own->prof.begin(PSFM_PROF_CHAIN, s);                    // (psfm_ctx_set_profiling on the owner: the tracking launches count as the chain step)
-        if (flows_f) qb_launch_track<false>(own, dtab, dend, blocks, mb, s);
-        if (flows_b) qb_launch_track<true>(own, dtab, dend, blocks, mb, s);
+        if (hooks) {
+            PsfmQbRun run;
+            run.own = own; run.ctxs = ctxs; run.n_seq = n_seq; run.tab_host = hs->up.tab; run.tab = dtab; run.blk_end = dend;
+            run.blocks = blocks; run.mb = mb; run.s = s;
+            if ((st = hooks->track(hooks->user, run)) != PSFM_OK) return st;
+        } else {
+            if (flows_f) qb_launch_track<false>(own, dtab, dend, blocks, mb, s);
+            if (flows_b) qb_launch_track<true>(own, dtab, dend, blocks, mb, s);
+        }
         own->prof.end(s);
         PSFM_HIP(hipGetLastError());
         own->prof.begin(PSFM_PROF_FINALIZE, s);                 // lengths -> offsets -> CSR as the finalize
@@ -394,10 +407,18 @@ extern "C" psfm_status psfm_track_queries_batch(psfm_ctx* const* ctxs, int n_seq
             info->n_points = c->res_n_points;
             info->n_lanes_peak = nq[i];
             info->lane_capacity = nq[i];
-            info->chain_mode = 6;
+            info->chain_mode = hooks ? hooks->chain_mode : 6;
         }
     }
     return PSFM_OK;
+}
+
+extern "C" psfm_status psfm_track_queries_batch(psfm_ctx* const* ctxs, int n_seq, const float* const* flows_f, const uint8_t* const* occ_f,
+                                                const float* const* flows_b, const uint8_t* const* occ_b, const int* n_flows, const int* h,
+                                                const int* w, const double* const* q_xy, const int32_t* const* q_t, const int64_t* n_q,
+                                                psfm_track_info* infos_host, void* stream)
+{
+    return psfm_qb_run(ctxs, n_seq, flows_f, occ_f, flows_b, occ_b, n_flows, h, w, q_xy, q_t, n_q, infos_host, stream, nullptr);
 }
 
 extern "C" psfm_status psfm_query_batch_census(psfm_ctx* c, int32_t* launches, int32_t* host_syncs)

@@ -1103,3 +1103,28 @@ psfm_status psfm_solve_batch(psfm_ctx* c, const double* uv12, const double* ref1
     PSFM_HIP(hipStreamSynchronize(s));
     return PSFM_OK;
 }
+
+// ---- the multi-problem launch chain (psfm_solver_multi.hip): one problem's buffers in its own context, as psfm_solve_batch sets them up ----
+psfm_status pc_multi_problem(psfm_ctx* c, int64_t cap, int h, int w, PcParams& P, int* limit, hipStream_t s)
+{
+    if (cap < 1 || cap > 0x3fffffff) { psfm_set_error("path-consistency solver: %lld rows", (long long)cap); return PSFM_ERR_ARG; }
+    psfm_status rc;
+    if ((rc = pc_workspace(c, cap, 2)) != PSFM_OK) return rc;
+    if ((rc = c->sol_misc.ensure(sizeof(double2) * cap * 2)) != PSFM_OK) return rc;
+    memset(&P, 0, sizeof(P));
+    P.H = h; P.W = w;
+    P.cw = (float)((double)(w - 1) / 2.0); P.ch = (float)((double)(h - 1) / 2.0);
+    P.n_rows = (int)cap;
+    P.x1a = c->sol_misc.as<double2>();
+    P.x2a = P.x1a + cap;
+    P.xs = c->sol_x.as<double2>(); P.xs_stride = cap;
+    P.ref1 = c->sol_state.as<double2>();
+    P.ref2 = P.ref1 + cap;
+    P.jscale = P.ref2 + cap;
+    P.scale = (double*)(P.jscale + cap);
+    if ((rc = pc_setup(c, P, s)) != PSFM_OK) return rc;       // (lists sized for cap rows: the most entries per block of any row count)
+    *limit = pc_blocks(c, 0x3fffffff);
+    return PSFM_OK;
+}
+
+void pc_multi_stats(const PsfmSolveCtrl* C, psfm_solve_stats* st) { pc_fill_stats(C, st); }

@@ -8,6 +8,31 @@ psfm_status pc_workspace(psfm_ctx* c, int64_t rows, int n_buf);
 psfm_status pc_frame_params(psfm_ctx* c, const PsfmTrackDims& d, const float* flow01, const float* flow12,
                             const float* flow02, const uint8_t* occ02, int frame, PcParams& P, hipStream_t s);
 
+// A batch-mode problem (rows given, no frame recurrence) of up to `cap` rows in c's OWN solver workspace, as psfm_solve_batch sets one
+// up -- pc_workspace(c, cap, 2) + pc_setup: iterate buffers, refs / jscale / scale, ctrl, ticket, partials, the lists sized for every
+// row count up to cap -- with buffer 0 (x1a, x2a) in c->sol_misc.  *limit: the blocks a launch of this context's chain may use (pc_blocks).
+psfm_status pc_multi_problem(psfm_ctx* c, int64_t cap, int h, int w, PcParams& P, int* limit, hipStream_t s);
+
+// ---- psfm_solver_multi.hip: the launch chain over a table of problems (index rules: psfm_solver_multi.h) ----
+// One problem of the table.  P.n_lanes_ptr: the address of the problem's row count for the current step; P.n_rows: the rows its
+// buffers hold; P.flow12: map 0 of the stack the solves sample (the kernels add pc_multi_map(k) * flow_stride).
+struct PcMultiRow {
+    PcParams P;
+    int64_t flow_stride;      // float2 elements between two maps of the stack
+    int n_flows;              // steps of the problem's sequence: it takes part in steps 1 .. n_flows - 1
+    int back;                 // the direction's map rule (pc_multi_map)
+    int limit;                // blocks a launch may use for this problem
+    int pad;
+};
+// what the poll leaves in pinned memory per problem
+struct PcMultiPoll { PsfmSolveCtrl C; int n_rows; int pad; };
+void pc_multi_launch_init(const PcMultiRow* tab, int grid_x, int n_problems, int k, hipStream_t s);
+void pc_multi_launch_iter(const PcMultiRow* tab, int grid_x, int n_problems, int k, int n_launches, hipStream_t s);
+void pc_multi_launch_writeback(const PcMultiRow* tab, int grid_x, int n_problems, int k, hipStream_t s);
+void pc_multi_launch_poll(const PcMultiRow* tab, int n_problems, int k, PcMultiPoll* out_pinned, hipStream_t s);
+// the statistics of a finished solve from its control block, as psfm_solve_batch reports them
+void pc_multi_stats(const PsfmSolveCtrl* C, psfm_solve_stats* st);
+
 // ---- psfm_solver_fused.hip ----
 psfm_status pc_fused_workspace(psfm_ctx* c, const PsfmTrackDims& d, PcParams& P, int K, hipStream_t s, bool zero_tickets = false);
 psfm_status pc_launch_fused_export(psfm_ctx* c, const PsfmTrackDims& d, PcParams& P, int K, hipStream_t s);

@@ -40,6 +40,7 @@ EXPORTS = [
     "psfm_track_queries", "psfm_track_queries_optimize",
     "psfm_result_filter_batch", "psfm_traj_to_matches_batch", "psfm_labels_to_matches_batch", "psfm_matches_batch_census", "psfm_labels_sizes",
     "psfm_track_queries_batch", "psfm_query_batch_census",
+    "psfm_track_queries_optimize_batch", "psfm_query_pc_batch_census",
 ]
 
 
@@ -110,6 +111,10 @@ def lib():
                                            ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(vp), ctypes.POINTER(vp),
                                            ctypes.POINTER(i64), ctypes.POINTER(TrackInfo), vp]
     L.psfm_query_batch_census.argtypes = [vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]
+    L.psfm_track_queries_optimize_batch.argtypes = [ctypes.POINTER(vp), i32] + [ctypes.POINTER(vp)] * 8 + [
+        ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(i64),
+        ctypes.POINTER(TrackInfo), vp]
+    L.psfm_query_pc_batch_census.argtypes = [vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]
     L.psfm_result_device.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp)]
     L.psfm_result_copy.argtypes = [vp, vp, vp, vp, vp, vp]
     L.psfm_result_solve_stats.argtypes = [vp, ctypes.POINTER(SolveStats), i32, ctypes.POINTER(ctypes.c_int32)]
@@ -288,6 +293,14 @@ class Context:
         a, b = ctypes.c_int32(), ctypes.c_int32()
         check(lib().psfm_query_batch_census(self._h, ctypes.byref(a), ctypes.byref(b)))
         return {"launches": int(a.value), "host_syncs": int(b.value)}
+
+    def query_pc_batch_census(self):
+        """The last psfm_track_queries_optimize_batch call that had this context as its first: launches that do not depend on how the
+        solves went (kernels and copies, the kill maps of the motion-boundary option apart), trust-region iteration launches, and
+        host synchronisations."""
+        a, b, c = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+        check(lib().psfm_query_pc_batch_census(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
+        return {"launches_fixed": int(a.value), "launches_iter": int(b.value), "host_syncs": int(c.value)}
 
     def set_sparse_depth(self, budget_bytes=1 << 30, timing=False):
         """psfm_sfm.convert: bytes of depth maps + winner maps (12 per pixel) one psfm_sparse_depth call may take (0: no limit; one

@@ -620,8 +620,19 @@ def run_track_queries_batch(seqs, motion_boundary=False, mb_thres=0.02, return_d
     Returns one TrajectoryList per sequence; with return_device=True (contexts, infos) -- context i holds sequence i's result until
     the calling thread's next batch -- which needs the list to fit one group.
     The stride-2 path-consistency form is out of scope (psfm_track_queries_optimize solves jointly per sequence with a host decision
-    per frame): a sequence that comes with flows_f2 / occ_f2 / flows_b2 / occ_b2 is a ValueError; use run_track_queries for it."""
+    per frame): a sequence that comes with flows_f2 / occ_f2 / flows_b2 / occ_b2 is a ValueError; use run_track_queries_pc_batch
+    (or run_track_queries) for it."""
+    return _track_queries_batch(seqs, motion_boundary, mb_thres, return_device, False)
+
+
+_STRIDE2 = (("flows_f2", "occ_f2"), ("flows_b2", "occ_b2"))
+
+
+def _track_queries_batch(seqs, motion_boundary, mb_thres, return_device, optimize):
+    """run_track_queries_batch (optimize False: stride-2 stacks are refused) and run_track_queries_pc_batch (optimize True: ONE
+    psfm_track_queries_optimize_batch call per group)."""
     import torch
+    who = "track_queries_pc_batch" if optimize else "track_queries_batch"
     n_seq = len(seqs)
     if n_seq < 1:
         return ([], []) if return_device else []
@@ -629,7 +640,7 @@ def run_track_queries_batch(seqs, motion_boundary=False, mb_thres=0.02, return_d
     if motion_boundary:
         mb_list = [float(mb_thres)] * n_seq if np.isscalar(mb_thres) else [float(v) for v in mb_thres]
         if len(mb_list) != n_seq:
-            raise ValueError("track_queries_batch: %d thresholds for %d sequences" % (len(mb_list), n_seq))
+            raise ValueError("%s: %d thresholds for %d sequences" % (who, len(mb_list), n_seq))
     first = _hip.context()
     dev = torch.device("cuda", first.device)
 
@@ -638,7 +649,7 @@ def run_track_queries_batch(seqs, motion_boundary=False, mb_thres=0.02, return_d
         return a.to(device=dev, dtype=dt)
     prepared, dirs0 = [], None
     for i, sq in enumerate(seqs):
-        if any(sq.get(k) is not None for k in ("flows_f2", "occ_f2", "flows_b2", "occ_b2")):
+        if not optimize and any(sq.get(k) is not None for k in ("flows_f2", "occ_f2", "flows_b2", "occ_b2")):
             raise ValueError("track_queries_batch: sequence %d comes with stride-2 stacks; path consistency for a batch of sequences "
                              "is out of scope, use run_track_queries for it" % i)
         m = {}
@@ -646,25 +657,37 @@ def run_track_queries_batch(seqs, motion_boundary=False, mb_thres=0.02, return_d
                                ("occ_b", torch.uint8, (1, 1))):
             m[name] = _as_device_stack(sq[name], dt, tail) if sq.get(name) is not None else None
         if (m["flows"] is None) != (m["occ"] is None) or (m["flows_b"] is None) != (m["occ_b"] is None) or (m["flows"] is None and m["flows_b"] is None):
-            raise ValueError("track_queries_batch: sequence %d: give at least one stack, and every stack with its occlusion maps" % i)
+            raise ValueError("%s: sequence %d: give at least one stack, and every stack with its occlusion maps" % (who, i))
         dirs = (m["flows"] is not None, m["flows_b"] is not None)
         if dirs0 is None:
             dirs0 = dirs
         elif dirs != dirs0:
-            raise ValueError("track_queries_batch: sequence %d gives other directions than sequence 0 (a direction is given for the whole batch)" % i)
+            raise ValueError("%s: sequence %d gives other directions than sequence 0 (a direction is given for the whole batch)" % (who, i))
         ref = m["flows"] if m["flows"] is not None else m["flows_b"]
         n, H, W = int(ref.shape[0]), int(ref.shape[1]), int(ref.shape[2])
         for name, tail in (("flows", (H, W, 2)), ("occ", (H, W)), ("flows_b", (H, W, 2)), ("occ_b", (H, W))):
             if m[name] is not None and (int(m[name].shape[0]) != n or tuple(m[name].shape[1:]) != tail):
-                raise ValueError("track_queries_batch: sequence %d: %s has shape %s, expected %s" % (i, name, tuple(m[name].shape), (n,) + tail))
+                raise ValueError("%s: sequence %d: %s has shape %s, expected %s" % (who, i, name, tuple(m[name].shape), (n,) + tail))
         q_xy = as_t(sq["xy"], torch.float64).reshape(-1, 2).contiguous()
         q_t = as_t(sq["t"], torch.int32).reshape(-1).contiguous()
         if q_t.shape[0] != q_xy.shape[0]:
-            raise ValueError("track_queries_batch: sequence %d: %d positions for %d frames" % (i, q_xy.shape[0], q_t.shape[0]))
-        prepared.append((m, n, H, W, q_xy, q_t))
+            raise ValueError("%s: sequence %d: %d positions for %d frames" % (who, i, q_xy.shape[0], q_t.shape[0]))
+        s2 = {}
+        if optimize:   # the stride-2 stacks: (n-1,H,W,2) and (n-1,H,W); empty (one flow) goes as NULL; the library refuses what does not fit
+            for f2, o2 in _STRIDE2:
+                for name, dt, tail in ((f2, torch.float32, (H, W, 2)), (o2, torch.uint8, (H, W))):
+                    a = sq.get(name)
+                    if a is None:
+                        s2[name] = None
+                        continue
+                    a = _as_device_stack(a, dt, (1, 1, 2) if len(tail) == 3 else (1, 1))
+                    if int(a.shape[0]) != n - 1 or (a.numel() > 0 and tuple(a.shape[1:]) != tail):
+                        raise ValueError("%s: sequence %d: %s has shape %s, expected %s" % (who, i, name, tuple(a.shape), (n - 1,) + tail))
+                    s2[name] = a if a.numel() > 0 else None
+        prepared.append((m, n, H, W, q_xy, q_t, s2))
     groups = _query_batch_groups([int(p[4].shape[0]) for p in prepared])
     if return_device and len(groups) > 1:
-        raise ValueError("track_queries_batch: return_device needs at most %d sequences and fewer than 2^28 queries (one call)" % QUERY_BATCH_MAX_SEQ)
+        raise ValueError("%s: return_device needs at most %d sequences and fewer than 2^28 queries (one call)" % (who, QUERY_BATCH_MAX_SEQ))
     vp = ctypes.c_void_p
     results = []
     for g0, g1 in groups:
@@ -673,7 +696,11 @@ def run_track_queries_batch(seqs, motion_boundary=False, mb_thres=0.02, return_d
         handles = (vp * B)(*[c.handle for c in ctxs])
         ff, of, fb, ob, qx, qt = ((vp * B)() for _ in range(6))
         nf, hh, ww, nq = (ctypes.c_int * B)(), (ctypes.c_int * B)(), (ctypes.c_int * B)(), (ctypes.c_int64 * B)()
-        for k, (m, n, H, W, q_xy, q_t) in enumerate(prepared[g0:g1]):
+        f2, o2, b2, p2 = ((vp * B)() for _ in range(4))
+        for k, (m, n, H, W, q_xy, q_t, s2) in enumerate(prepared[g0:g1]):
+            for arr, name in ((f2, "flows_f2"), (o2, "occ_f2"), (b2, "flows_b2"), (p2, "occ_b2")):
+                if s2.get(name) is not None:
+                    arr[k] = s2[name].data_ptr()
             if dirs0[0]:
                 ff[k], of[k] = m["flows"].data_ptr(), m["occ"].data_ptr()
             if dirs0[1]:
@@ -682,13 +709,23 @@ def run_track_queries_batch(seqs, motion_boundary=False, mb_thres=0.02, return_d
             if nq[k] > 0:
                 qx[k], qt[k] = q_xy.data_ptr(), q_t.data_ptr()
         infos = (_hip.TrackInfo * B)()
+
+        def given(d, name):     # a stride-2 array goes with its direction, or when some sequence brings an entry for it
+            return dirs0[d] or any(p[6].get(name) is not None for p in prepared[g0:g1])
         try:
             if mb_list is not None:
                 for c, v in zip(ctxs, mb_list[g0:g1]):
                     c.set_motion_boundary(True, v)
-            st = _hip.lib().psfm_track_queries_batch(handles, B, ff if dirs0[0] else None, of if dirs0[0] else None, fb if dirs0[1] else None,
-                                                     ob if dirs0[1] else None, nf, hh, ww, qx, qt, nq, infos,
-                                                     _hip.current_stream_ptr(ctxs[0].device))
+            if optimize:
+                st = _hip.lib().psfm_track_queries_optimize_batch(
+                    handles, B, ff if dirs0[0] else None, of if dirs0[0] else None, f2 if given(0, "flows_f2") else None,
+                    o2 if given(0, "occ_f2") else None, fb if dirs0[1] else None, ob if dirs0[1] else None,
+                    b2 if given(1, "flows_b2") else None, p2 if given(1, "occ_b2") else None,
+                    nf, hh, ww, qx, qt, nq, infos, _hip.current_stream_ptr(ctxs[0].device))
+            else:
+                st = _hip.lib().psfm_track_queries_batch(handles, B, ff if dirs0[0] else None, of if dirs0[0] else None, fb if dirs0[1] else None,
+                                                         ob if dirs0[1] else None, nf, hh, ww, qx, qt, nq, infos,
+                                                         _hip.current_stream_ptr(ctxs[0].device))
         finally:
             if mb_list is not None:      # (the option is per context and the thread's batch contexts are reused: off again, whatever happened)
                 for c in ctxs:
@@ -726,3 +763,55 @@ def run_connect_queries_batch(seqs, thres=1.0, direction="forward", motion_bound
             kw.update(flows_b=fb, occ_b=flow_check_device(fb, ff, thres)[1])
         out.append(kw)
     return run_track_queries_batch(out, motion_boundary=motion_boundary, mb_thres=mb_thres, return_device=return_device)
+
+
+def run_track_queries_pc_batch(seqs, motion_boundary=False, mb_thres=0.02, return_device=False):
+    """run_track_queries WITH the stride-2 path-consistency solve for a LIST of sequences, in one psfm_track_queries_optimize_batch call
+    per group of at most 64 sequences (and fewer than 2^28 queries): per step ONE set of launches covers every sequence -- the step,
+    the row scan, the rows, the multi-problem solve (one grid over all sequences' solves), one poll with one synchronisation, the
+    write-back -- so a directory of small videos pays the fixed cost of a frame once.  seqs: the dicts of run_track_queries_batch plus
+    the stride-2 keys of run_track_queries: `flows_f2`, `occ_f2` (with `flows`, `occ`) and / or `flows_b2`, `occ_b2` (with `flows_b`,
+    `occ_b`), (n-1,H,W,2) and (n-1,H,W); a sequence of one flow may leave them out or give empty stacks.  Each sequence keeps its own
+    frame size, length and query count.  Sequence i's result -- births, lengths, offsets, positions, solve statistics -- is that of
+    run_track_queries(... stride-2 ...) on it alone; R.info["chain_mode"] is 7, R.info["n_solves"] and ["solver_iterations"] are the
+    sequence's own.  motion_boundary / mb_thres, return_device and the refusals: as run_track_queries_batch, and a direction whose
+    stride-1 stack lacks its stride-2 stack in a sequence of two or more flows is refused by the library (PsfmError, naming the
+    sequence)."""
+    return _track_queries_batch(seqs, motion_boundary, mb_thres, return_device, True)
+
+
+def run_connect_queries_pc_batch(seqs, thres=1.0, direction="forward", motion_boundary=False, mb_thres=0.02, return_device=False):
+    """flow_check + run_track_queries_pc_batch: seqs are dicts with `xy`, `t`, `flows_f`, `flows_b` ((n,H,W,2), flows_b[f]: frame f+1 ->
+    f) and `flows_f2`, `flows_b2` ((n-1,H,W,2), flows_b2[f]: frame f+2 -> f).  Each direction's stride-1 and stride-2 occlusion maps
+    come from flow_check_device in that direction's orientation, as in run_connect_queries -- forward: flow_check(flows_f, flows_b)
+    and flow_check(flows_f2, flows_b2); backward: flow_check(flows_b, flows_f) and flow_check(flows_b2, flows_f2).  direction:
+    "forward", "backward" or "both", for the whole batch."""
+    import torch
+    from .utils import flow_check_device
+    if direction not in ("forward", "backward", "both"):
+        raise ValueError("connect_queries_pc_batch: direction must be 'forward', 'backward' or 'both'")
+    out = []
+    for i, sq in enumerate(seqs):
+        ff = _as_device_stack(sq["flows_f"], torch.float32, (1, 1, 2))
+        fb = _as_device_stack(sq["flows_b"], torch.float32, (1, 1, 2))
+        n = min(int(ff.shape[0]), int(fb.shape[0]))
+        ff, fb = ff[:n], fb[:n]
+        f2 = b2 = None
+        if n > 1:
+            if sq.get("flows_f2") is None or sq.get("flows_b2") is None:
+                raise ValueError("connect_queries_pc_batch: sequence %d: the stride-2 maps of either direction need both stride-2 stacks" % i)
+            f2 = _as_device_stack(sq["flows_f2"], torch.float32, (1, 1, 2))[:n - 1]
+            b2 = _as_device_stack(sq["flows_b2"], torch.float32, (1, 1, 2))[:n - 1]
+            if int(f2.shape[0]) != n - 1 or int(b2.shape[0]) != n - 1:
+                raise ValueError("connect_queries_pc_batch: sequence %d: need %d stride-2 flows per direction" % (i, n - 1))
+        kw = dict(xy=sq["xy"], t=sq["t"])
+        if direction in ("forward", "both"):
+            kw.update(flows=ff, occ=flow_check_device(ff, fb, thres)[1])
+            if f2 is not None:
+                kw.update(flows_f2=f2, occ_f2=flow_check_device(f2, b2, thres)[1])
+        if direction in ("backward", "both"):
+            kw.update(flows_b=fb, occ_b=flow_check_device(fb, ff, thres)[1])
+            if f2 is not None:
+                kw.update(flows_b2=b2, occ_b2=flow_check_device(b2, f2, thres)[1])
+        out.append(kw)
+    return run_track_queries_pc_batch(out, motion_boundary=motion_boundary, mb_thres=mb_thres, return_device=return_device)
