@@ -86,7 +86,9 @@ typedef struct psfm_solve_stats {
 typedef struct psfm_track_info {
     int64_t n_traj;            /* all trajectories, index == id (full_trajs order) */
     int64_t n_points;          /* sum of their lengths */
-    int64_t n_lanes_peak;      /* peak number of lanes used (<= lane capacity) */
+    int64_t n_lanes_peak;      /* peak number of lanes used (<= lane capacity): the high-water mark of the lane allocator, whose blocks
+                                  take and return lanes concurrently inside one launch -- it may differ by a few lanes between two
+                                  identical calls; no id, length or position depends on the lane a track sat in */
     int64_t lane_capacity;
     int64_t solver_iterations; /* total trust-region iterations over all frames (track_optimize) */
     int32_t n_solves;
@@ -274,7 +276,12 @@ psfm_status psfm_track(psfm_ctx* ctx, const float* flows, const uint8_t* occ, co
  *   - otherwise the maps are produced on an internal side stream while the frame loop consumes them.
  *   flows_f, flows_b   (n_flows,H,W,2) f32      flows_f2, flows_b2  (n_flows-1,H,W,2) f32 or NULL
  *   occ, occ_s2        optional outputs (n_flows,H,W) / (n_flows-1,H,W) u8; NULL = kept in the context
- * Result access as for psfm_track.  Synchronises `stream`. */
+ * Result access as for psfm_track.  Synchronises `stream`.
+ * Reproducibility: in track mode two identical calls give identical bytes.  With the stride-2 solve (flows_f2 != NULL; psfm_track
+ * and psfm_connect_batch likewise) they give identical ids, births, lengths and solver decisions, but no promise is made for the
+ * last bits: a solve's final_cost has been observed to differ by one unit in the last place between two identical calls (the
+ * adaptive policy of psfm_ctx_set_solver carries over from call to call; and with the form forced, in psfm_connect_batch), and
+ * positions are held to 1e-9 px between two runs, as between the batched and the single form. */
 psfm_status psfm_connect(psfm_ctx* ctx, const float* flows_f, const float* flows_b, const float* flows_f2,
                          const float* flows_b2, int n_flows, int h, int w, float thres, int sample_ratio,
                          uint8_t* occ, uint8_t* occ_s2, psfm_track_info* info_host, void* stream);
@@ -332,7 +339,9 @@ psfm_status psfm_track_queries(psfm_ctx* ctx, const float* flows_f, const uint8_
  * does (trajectory i is query i, info->n_traj = n_q, a live label merge is void, psfm_result_keys refuses it); info->chain_mode = 5.
  * psfm_result_solve_stats: one entry per solve that ran, forward frames ascending, then backward frames in the order they ran
  * (descending).  The solve is the one psfm_optimize_location runs and honours psfm_ctx_set_solver / psfm_ctx_set_resident_budget as
- * it does.  One small device-to-host copy per frame (the row count).  Synchronises `stream`. */
+ * it does.  One small device-to-host copy per frame (the row count).  Synchronises `stream`.  No promise of identical bytes from
+ * identical calls is made here (psfm_track_queries_optimize_batch makes one for its launch-chain form): decisions are the same,
+ * positions are held to 1e-9 px between two runs. */
 psfm_status psfm_track_queries_optimize(psfm_ctx* ctx, const float* flows_f, const uint8_t* occ_f, const float* flows_f2,
                                         const uint8_t* occ_f2, const float* flows_b, const uint8_t* occ_b, const float* flows_b2,
                                         const uint8_t* occ_b2, int n_flows, int h, int w, const double* q_xy, const int32_t* q_t,
@@ -666,6 +675,8 @@ psfm_status psfm_matches_copy(psfm_ctx* ctx, int64_t* kp_off_host, double* kp_xy
  * psfm_labels_begin         needs a non-empty saved set in the context (else PSFM_ERR_ARG); clears the merge state and ties it to
  *                           that saved set: a later psfm_result_filter / psfm_track / psfm_connect / psfm_connect_batch on the
  *                           context voids it, and psfm_labels_merge_window / psfm_labels_finish then return PSFM_ERR_ARG.
+ *                           ASYNCHRONOUS: three memsets on `stream`, no host synchronisation (the merge state is allocated by the
+ *                           first call for a saved set of that size and grows with it).
  * psfm_labels_merge_window  one window, in stream order: row i says trajectory ids_dev[i] (i32, an id of the saved set) is dynamic
  *                           (pred_dev[i] != 0) or static on frames [frame0, frame0 + n_frames).  ASYNCHRONOUS: one launch, no host
  *                           synchronisation, no allocation -- it can be enqueued right behind the network's output tensor.  k = 0 is
