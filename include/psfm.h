@@ -52,7 +52,8 @@
 extern "C" {
 #endif
 
-#define PSFM_VERSION 141   /* round 5: psfm_connect_batch */
+#define PSFM_VERSION 141   /* round 5: psfm_connect_batch.  Not moved by later exports (psfm_ctx_set_batch_redo and psfm_connect_batch_census
+                              among them): tests/test_abi_and_host.py pins the number, and callers find an export by its symbol */
 
 typedef enum psfm_status {
     PSFM_OK = 0,
@@ -98,7 +99,9 @@ typedef struct psfm_track_info {
                                   with the path-consistency solve (psfm_track_queries_optimize), 6 one launch per direction over the
                                   query points of a whole batch of sequences (psfm_track_queries_batch), 7 one loop of launches over
                                   the steps of a whole batch of sequences with the multi-problem path-consistency solve
-                                  (psfm_track_queries_optimize_batch) */
+                                  (psfm_track_queries_optimize_batch), 8 one chain step per frame for the sequences that left a batch,
+                                  their solves as the frame-mode multi-problem launch chain (psfm_connect_batch with
+                                  psfm_ctx_set_batch_redo(ctxs[0], 1)) */
 } psfm_track_info;
 
 const char* psfm_last_error(void);
@@ -437,10 +440,39 @@ psfm_status psfm_query_pc_batch_census(psfm_ctx* ctx, int32_t* launches_fixed, i
  * Motion boundary (psfm_ctx_set_motion_boundary): on in EVERY context of the batch, each with its own threshold, or in none; contexts
  * that disagree are PSFM_ERR_ARG.  With it on every frame launch forms the second verdict from the sequences' kill maps, which are
  * built for all sequences together (psfm_kill_map_batch's launch) behind each chunk of flow_check; results are those of psfm_connect
- * with the option on, sequence by sequence, and info->chain_mode is 3 for a sequence that stayed in the batch. */
+ * with the option on, sequence by sequence, and info->chain_mode is 3 for a sequence that stayed in the batch.
+ * Sequences that leave the batch, together (psfm_ctx_set_batch_redo(ctxs[0], 1); default 0: alone, as above): they are run again from
+ * frame 0 through ONE set of launches -- the batched chain step of every frame and, behind it, the frame's solves of all of them
+ * as the frame-mode multi-problem launch chain: one init launch, iteration launches paced by one poll and ONE host synchronisation
+ * for all sequences, one write-back launch -- and one segmented finalize; launches only, the device is never taken exclusively.  With
+ * the option on a context pinned to the launch chain (psfm_ctx_set_solver mode 1) goes there directly.  info->chain_mode is 8 for a
+ * sequence that ran this way.  Against what psfm_connect leaves for that sequence alone on a context pinned to the launch chain
+ * (psfm_ctx_set_solver(ctx, 1, 0)) with no resident budget, the same lane capacity and the same motion-boundary setting, it holds:
+ * ids, births, lengths, offsets and every solve's iterations, successful steps, termination and non-Gauss-Newton count are EXACT.
+ * Positions and the two costs of a solve are what psfm_track promises between two runs of one sequence, no more: the block count,
+ * the list plan, the order of the block sums and the control step are the single chain's, so they are byte-equal where the lanes
+ * were handed out alike (a solve's sums run in lane order, and lanes are handed out by blocks that race inside a chain step), and
+ * positions agree to <= 1e-9 px otherwise.  Observed on an MI355X: all bytes equal on sequences of up to 6 000 grid points with few
+ * respawns; the last bit of a cost on 12 288 dense points; positions to 1e-13 px on realistic flows of 25 000 to 307 000 points.
+ * Where the capacities differ, the same <= 1e-9 px holds.  Sequences that stayed in the batch are untouched by the option.
+ * psfm_connect_batch_census: the last call that had `ctx0` as ctxs[0] -- n_left (sequences that left the fused batch), n_together
+ * (those that went through the joint redo), and of that redo launches_fixed (the table copy, the lane-table init, one chain step
+ * per frame, per frame with a solve the init launch, the polls and the write-back launch), launches_iter (trust-region iteration
+ * launches, each over all sequences) and host_syncs (one per poll, one behind the finalize): per frame the fixed launches are
+ * three (chain step, init, write-back) whatever n_together is; polls, iteration launches and synchronisations are set by the
+ * SLOWEST solve of the frame in the table -- they do not grow with the number of sequences beyond that solve's need, but a further
+ * sequence whose solve is the slowest of a frame adds a chunk of iteration launches and a poll there.
+ * The joint redo files its solves in each context's adaptive policy (psfm_ctx_set_solver mode 0: launch chain or fused solve next,
+ * iterations per fused launch), as the checkpoints of psfm_connect do for a sequence redone alone, over the whole sequence instead
+ * of its last window: what a context starts its next call with may differ between the two routes. */
 psfm_status psfm_connect_batch(psfm_ctx* const* ctxs, int n_seq, const float* const* flows_f, const float* const* flows_b,
                                const float* const* flows_f2, const float* const* flows_b2, const int* n_flows, int h, int w,
                                float thres, int sample_ratio, psfm_track_info* infos_host, void* stream);
+/* mode 0: sequences that leave the fused batch run alone through psfm_connect (default); 1: together (see above).  Read from ctxs[0]
+ * of a psfm_connect_batch call.  Any other value: PSFM_ERR_ARG. */
+psfm_status psfm_ctx_set_batch_redo(psfm_ctx* ctx, int mode);
+psfm_status psfm_connect_batch_census(psfm_ctx* ctx0, int32_t* n_left, int32_t* n_together, int32_t* launches_fixed,
+                                      int32_t* launches_iter, int32_t* host_syncs);
 
 /* Device-resident result of the last psfm_track: CSR over trajectories in id order.
  *   birth (n_traj) i32 first frame; len (n_traj) i32; off (n_traj+1) i64; xy (n_points,2) f64.

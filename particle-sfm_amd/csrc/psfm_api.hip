@@ -233,6 +233,13 @@ extern "C" psfm_status psfm_ctx_set_solver(psfm_ctx* c, int mode, int k)
     return PSFM_OK;
 }
 
+extern "C" psfm_status psfm_ctx_set_batch_redo(psfm_ctx* c, int mode)
+{
+    if (!c || mode < 0 || mode > 1) { psfm_set_error("psfm_ctx_set_batch_redo: mode must be 0 (alone) or 1 (together)"); return PSFM_ERR_ARG; }
+    c->batch_redo = mode;
+    return PSFM_OK;
+}
+
 extern "C" psfm_status psfm_solver_counters(psfm_ctx* c, int64_t* fused, int64_t* fused_redone, int64_t* chain, int32_t* k_now)
 {
     if (!c) { psfm_set_error("ctx is NULL"); return PSFM_ERR_ARG; }

@@ -16,7 +16,9 @@
 //   * ONE checkpoint (one packed copy, one synchronisation) per window of frames for all sequences, and ONE segmented finalize
 //     (psfm_finalize_batch: one sort over the records of all sequences);
 //   * a sequence whose solves reject steps (what the launch chain / the resident solve are for) is redone at the checkpoint like in
-//     psfm_track; when a whole window of it is like that it leaves the batch and runs alone through psfm_connect afterwards.
+//     psfm_track; when a whole window of it is like that it leaves the batch and runs alone through psfm_connect afterwards
+//     (redo_alone) -- or, with psfm_ctx_set_batch_redo(ctxs[0], 1), together with the others that left: one batched chain step per
+//     frame and the frame's solves as the frame-mode multi-problem launch chain (redo_together, psfm_solver_multi.hip).
 //   * psfm_ctx_set_motion_boundary on EVERY context of the batch: the frame launches are the MB forms of the two kernels
 //     (psfm_motion_boundary.hip, psfm_solver_batch_mb.hip) and sample every sequence's kill maps (c->kill), built by ONE launch per
 //     flow_check chunk for all sequences (psfm_kill_map_batch_kernel); contexts that disagree are refused.
@@ -31,6 +33,7 @@
 #include "psfm_internal.h"
 #include "psfm_chain_step.h"
 #include "psfm_solve_policy.h"
+#include "psfm_batch_chain.h"
 
 namespace {
 struct SeqState {
@@ -150,7 +153,11 @@ struct BatchRun {
     size_t pack_row = 0, pack_bytes = 0;
     char* hpack = nullptr;       // the packed checkpoint of all sequences on the host
     PsfmBatchSeq* dtab = nullptr; char* dtabo = nullptr;      // the tables of sequences on the device: chain-step rows, track_optimize rows
+    bool together = false;       // psfm_ctx_set_batch_redo(own, 1): sequences that leave the fused batch are redone by redo_together
 
+    // (a sequence sent out before the first window has no maps of its own yet: redo_alone's psfm_connect makes them, redo_together
+    // reads the batch's)
+    bool no_maps(int i) const { return S[i].dropped && !together; }
     psfm_status prepare();
     psfm_status flow_check();
     psfm_status tables();
@@ -158,6 +165,7 @@ struct BatchRun {
     psfm_status optimize_loop();
     psfm_status finalize(psfm_track_info* infos, std::vector<int>& redo);
     psfm_status redo_alone(const std::vector<int>& redo, psfm_track_info* infos, void* stream);
+    psfm_status redo_together(const std::vector<int>& redo, psfm_track_info* infos);
 };
 
 // ---- dimensions (one key format for the whole batch: the time bits of its longest sequence), workspaces ----
@@ -185,8 +193,9 @@ psfm_status BatchRun::prepare()
         if (D[i].cap > cap_max) cap_max = D[i].cap;
         if (D[i].G + D[i].G / 8 + 2048 > grid_lanes) grid_lanes = D[i].G + D[i].G / 8 + 2048;
         S[i].hstats.assign((size_t)n_flows[i] + 1, psfm_solve_stats());
-        // a context told to use the launch chain for every solve has nothing to gain from the batch: it runs alone
-        if (optimize && c->solver_mode == 1 && n_flows[i] >= 2) S[i].dropped = true;
+        // a context told to use the launch chain for every solve has nothing to gain from the fused batch: it runs alone -- or, with
+        // psfm_ctx_set_batch_redo(own, 1), straight through redo_together, on the maps this run's flow_check makes for it
+        if (optimize && c->solver_mode == 1 && (n_flows[i] >= 2 || together)) S[i].dropped = true;
     }
     if (trim && getenv("PSFM_BATCH_GRID_LANES")) grid_lanes = atoll(getenv("PSFM_BATCH_GRID_LANES"));      // (tests: launches that cover too little)
     if (!trim || grid_lanes > cap_max || grid_lanes < 256) grid_lanes = cap_max;
@@ -207,7 +216,7 @@ psfm_status BatchRun::flow_check()
     const int fc_env = getenv("PSFM_BATCH_FC_CHUNK") ? atoi(getenv("PSFM_BATCH_FC_CHUNK")) : -1;
     int fc_chunk = fc_env >= 0 ? fc_env : (optimize ? 6 : 8);
     for (int i = 0; i < B && fc_chunk > 0; ++i) {
-        if (S[i].dropped) continue;
+        if (no_maps(i)) continue;
         if (!psfm_flow_check_batch_ok(h, w, flows_f[i], flows_b[i], ctxs[i]->occ_own.p)) fc_chunk = 0;
         if (optimize && n_flows[i] > 1 && !psfm_flow_check_batch_ok(h, w, flows_f2[i], flows_b2[i], ctxs[i]->occ2_own.p)) fc_chunk = 0;
     }
@@ -215,7 +224,7 @@ psfm_status BatchRun::flow_check()
     own->prof.begin(PSFM_PROF_FLOW_CHECK, s);
     if (fc_chunk <= 0) {
         for (int i = 0; i < B; ++i) {
-            if (S[i].dropped) continue;
+            if (no_maps(i)) continue;
             psfm_ctx* c = ctxs[i];
             if ((st = psfm_launch_flow_check(flows_f[i], flows_b[i], n_flows[i], h, w, thres, c->occ_own.as<uint8_t>(), nullptr, s)) != PSFM_OK) return st;
             if (optimize && n_flows[i] > 1 &&
@@ -234,10 +243,10 @@ psfm_status BatchRun::flow_check()
     PsfmKmSeq* hkm = (PsfmKmSeq*)((char*)own->host_batch2 + fc_bytes);
     for (int i = 0; i < B; ++i) {
         psfm_ctx* c = ctxs[i];
-        hfc[i].ff = flows_f[i]; hfc[i].fb = flows_b[i]; hfc[i].occ = c->occ_own.as<uint8_t>(); hfc[i].n_pairs = S[i].dropped ? 0 : n_flows[i]; hfc[i].pad = 0;
+        hfc[i].ff = flows_f[i]; hfc[i].fb = flows_b[i]; hfc[i].occ = c->occ_own.as<uint8_t>(); hfc[i].n_pairs = no_maps(i) ? 0 : n_flows[i]; hfc[i].pad = 0;
         hfc[B + i].ff = optimize ? flows_f2[i] : nullptr; hfc[B + i].fb = optimize ? flows_b2[i] : nullptr;
         hfc[B + i].occ = optimize ? c->occ2_own.as<uint8_t>() : nullptr;
-        hfc[B + i].n_pairs = (optimize && !S[i].dropped && n_flows[i] > 1) ? n_flows[i] - 1 : 0; hfc[B + i].pad = 0;
+        hfc[B + i].n_pairs = (optimize && !no_maps(i) && n_flows[i] > 1) ? n_flows[i] - 1 : 0; hfc[B + i].pad = 0;
         if (mb) {
             hkm[i].flows = flows_f[i]; hkm[i].occ = c->occ_own.as<uint8_t>(); hkm[i].out = c->kill.as<uint8_t>();
             hkm[i].n = hfc[i].n_pairs; hkm[i].thres = c->mb_thres;
@@ -549,6 +558,99 @@ psfm_status BatchRun::redo_alone(const std::vector<int>& redo, psfm_track_info* 
         if (rc[(size_t)t] != PSFM_OK) { psfm_set_error("psfm_connect_batch: a sequence that left the batch failed: %s", msg[(size_t)t].c_str()); return rc[(size_t)t]; }
     return PSFM_OK;
 }
+
+// ---- sequences that left the batch, TOGETHER (psfm_ctx_set_batch_redo(own, 1)): from frame 0 again, as redo_alone does, but through
+// one set of launches -- the batched chain step of every frame, and behind it the frame's solves of ALL these sequences as the
+// frame-mode multi-problem launch chain (psfm_solver_multi.hip: one init launch, iteration launches paced by ONE poll and ONE
+// synchronisation for the whole table, one write-back launch), then one segmented finalize.  Every sequence's launches are block
+// for block those psfm_connect makes for it alone on a context pinned to the launch chain: the same bytes.  The sequences' maps
+// (occlusion, stride-2 occlusion, kill maps) are the ones this run's flow_check made; launches only, the gate stays shared. ----
+psfm_status BatchRun::redo_together(const std::vector<int>& redo, psfm_track_info* infos)
+{
+    psfm_status st;
+    const int n = (int)redo.size();
+    if (n == 0) return PSFM_OK;
+    PsfmGate gate(own->device, 0);
+    const size_t row_opt = psfm_batch_seq_opt_bytes(), row_fr = psfm_frame_row_bytes();
+    const size_t tab_bytes = sizeof(PsfmBatchSeq) * (size_t)n, fr_bytes = row_fr * (size_t)n, opt_bytes = row_opt * (size_t)n;
+    const size_t poll_bytes = psfm_frame_poll_bytes() * (size_t)n;
+    // (nothing of the fused run is in flight: finalize synchronised the stream -- its tables and staging are free to be replaced)
+    if ((st = batch_host_staging(own, tab_bytes + fr_bytes + opt_bytes + poll_bytes)) != PSFM_OK) return st;
+    if ((st = own->batch_tab.ensure(tab_bytes + fr_bytes)) != PSFM_OK) return st;
+    PsfmBatchSeq* htab = (PsfmBatchSeq*)own->host_batch;
+    char* hfr = (char*)own->host_batch + tab_bytes;
+    char* hopt = hfr + fr_bytes;                 // (the track_optimize rows the frame rows are cut from: never uploaded)
+    char* hpoll = hopt + opt_bytes;
+    const PsfmBatchSeq* dt = own->batch_tab.as<PsfmBatchSeq>();
+    const char* dfr = (const char*)own->batch_tab.p + tab_bytes;
+    int nb[PSFM_BATCH_MAX], n_top = 0;
+    int64_t cap_top = 0;
+    for (int q = 0; q < n; ++q) {
+        const int i = redo[q];
+        psfm_ctx* c = ctxs[i];
+        psfm_call_begin(c, n_flows[i], false);       // (a sequence that left at a checkpoint has solves on file: from the top)
+        S[i].total_iters = 0;
+        const uint8_t* masks = mb ? c->kill.as<uint8_t>() : c->occ_own.as<uint8_t>();
+        psfm_batch_fill_seq(c, D[i], flows_f[i], masks, P, &htab[q]);      // (owner_clear: the stamp-wrap clear of the blocked map, on the device)
+        const float* f2 = n_flows[i] > 1 ? flows_f2[i] : flows_f[i];
+        if ((st = psfm_batch_fill_seq_opt(c, D[i], flows_f[i], masks, P, f2, c->occ2_own.as<uint8_t>(), hopt + row_opt * (size_t)q, s)) != PSFM_OK) return st;
+        if ((st = psfm_frame_row_fill(c, D[i], hopt + row_opt * (size_t)q, hfr + row_fr * (size_t)q, &nb[q])) != PSFM_OK) return st;
+        if (n_flows[i] > n_top) n_top = n_flows[i];
+        if (D[i].cap > cap_top) cap_top = D[i].cap;
+    }
+    const int grid_x = pc_frame_grid_x(nb, n), kmax = psfm_solve_kmax();
+    std::vector<PsfmWindowTally> tally((size_t)n);
+    PSFM_HIP(hipMemcpyAsync(own->batch_tab.p, htab, tab_bytes + fr_bytes, hipMemcpyHostToDevice, s));
+    if ((st = psfm_launch_track_init_batch(dt, n, cap_top, s)) != PSFM_OK) return st;
+    own->bt_fixed += 2;
+    for (int f = 0; f < n_top; ++f) {
+        if ((st = psfm_launch_chain_step_batch(own, dt, n, ratio, cap_top, f, true, mb, s)) != PSFM_OK) return st;
+        own->bt_fixed += 1;
+        if (f < 1) continue;
+        if ((st = psfm_frame_solve_batch(dfr, grid_x, n, f, hpoll, &own->bt_fixed, &own->bt_iter, &own->bt_syncs, s)) != PSFM_OK) return st;
+        for (int q = 0; q < n; ++q) {
+            const int i = redo[q];
+            psfm_ctx* c = ctxs[i];
+            int active = 0, lanes = 0, overflow = 0, stall = 0;
+            psfm_solve_stats ss;
+            psfm_frame_poll_read(hpoll, q, &active, &ss, &lanes, &overflow, &stall);
+            if ((overflow & 7) != 0 || lanes > D[i].cap) {      // (as the checkpoint of the fused batch: a full table ends the run here)
+                psfm_set_error("capacity exceeded (sequence %d of the batch): lanes used %d of %lld, overflow bits %d; raise psfm_ctx_set_capacity",
+                               i, lanes, (long long)D[i].cap, overflow);
+                return PSFM_ERR_CAPACITY;
+            }
+            // (nothing on this path raises the stall flag -- track_init clears it, only fused and enqueued resident solves set it; a
+            // raised flag means the frame's launches skipped the sequence and the polled control block is an earlier frame's)
+            if (stall) { psfm_set_error("psfm_connect_batch: sequence %d has its stall flag raised (frame %d) inside the joint redo", i, stall - 1); return PSFM_ERR_SOLVER; }
+            if (!active || ss.termination < 0) continue;      // -1: no track had a full buffer, nothing was solved
+            c->solve_stats.push_back(ss);
+            S[i].total_iters += ss.iterations;
+            ++c->n_chain;
+            tally[(size_t)q].add(ss, kmax);
+        }
+    }
+    // what the context's adaptive policy takes into its next call (psfm_solve_policy.h), as the checkpoints of psfm_connect leave it:
+    // a sequence that left because of a stale K, not because its solves reject steps, starts the next batch with the K it needs
+    for (int q = 0; q < n; ++q) {
+        if (tally[(size_t)q].n_solved == 0) continue;
+        ctxs[redo[q]]->solve_mode = tally[(size_t)q].mode_next();
+        ctxs[redo[q]]->solve_K = tally[(size_t)q].k_device_paced(kmax);
+    }
+    std::vector<psfm_ctx*> kc;
+    std::vector<PsfmTrackDims> kd;
+    for (int i : redo) { kc.push_back(ctxs[i]); kd.push_back(D[i]); }
+    own->prof.begin(PSFM_PROF_FINALIZE, s);
+    st = psfm_finalize_batch(own, kc.data(), kd.data(), n, s);
+    own->prof.end(s);
+    if (st != PSFM_OK) return st;
+    PSFM_HIP(hipStreamSynchronize(s));
+    own->bt_syncs += 1;
+    own->prof.collect();
+    own->bt_together = n;
+    if (infos)
+        for (int i : redo) psfm_fill_track_info(&infos[i], ctxs[i], D[i].cap, S[i].total_iters, 8);
+    return PSFM_OK;
+}
 }  // namespace
 
 static psfm_status batch_run(psfm_ctx* const* ctxs, int n_seq, const float* const* flows_f, const float* const* flows_b,
@@ -560,6 +662,15 @@ static psfm_status batch_run(psfm_ctx* const* ctxs, int n_seq, const float* cons
     BatchRun R{ctxs, n_seq, flows_f, flows_b, flows_f2, flows_b2, n_flows, h, w, thres, ratio, (hipStream_t)stream, trim, grid_too_small,
                ctxs[0], flows_f2 != nullptr, ctxs[0]->mb_enable, (int64_t)h * w, PsfmOccPipeline(ctxs[0])};
     PSFM_HIP(hipSetDevice(R.own->device));
+    // how the sequences that leave the fused batch are redone: the owner's psfm_ctx_set_batch_redo; PSFM_BATCH_REDO=together|alone
+    // overrides it (measurements; read per call)
+    R.together = R.own->batch_redo == 1;
+    if (const char* e = getenv("PSFM_BATCH_REDO")) {
+        if (!strcmp(e, "together")) R.together = true;
+        else if (!strcmp(e, "alone")) R.together = false;
+    }
+    R.together = R.together && R.optimize;
+    R.own->bt_left = R.own->bt_together = R.own->bt_fixed = R.own->bt_iter = R.own->bt_syncs = 0;
     std::vector<int> redo;
     psfm_status st;
     {
@@ -570,6 +681,20 @@ static psfm_status batch_run(psfm_ctx* const* ctxs, int n_seq, const float* cons
         if ((st = R.optimize ? R.optimize_loop() : R.track_loop()) != PSFM_OK) return st;
         if ((st = R.finalize(infos, redo)) != PSFM_OK) return st;
     }
+    R.own->bt_left = (int32_t)redo.size();
+    if (R.together) return R.redo_together(redo, infos);
     return R.redo_alone(redo, infos, stream);
+}
+
+extern "C" psfm_status psfm_connect_batch_census(psfm_ctx* ctx0, int32_t* n_left, int32_t* n_together, int32_t* launches_fixed,
+                                                 int32_t* launches_iter, int32_t* host_syncs)
+{
+    if (!ctx0) { psfm_set_error("ctx is NULL"); return PSFM_ERR_ARG; }
+    if (n_left) *n_left = ctx0->bt_left;
+    if (n_together) *n_together = ctx0->bt_together;
+    if (launches_fixed) *launches_fixed = ctx0->bt_fixed;
+    if (launches_iter) *launches_iter = ctx0->bt_iter;
+    if (host_syncs) *host_syncs = ctx0->bt_syncs;
+    return PSFM_OK;
 }
 

@@ -223,6 +223,11 @@ struct psfm_ctx {
     void* host_batch2 = nullptr;
     size_t host_batch2_bytes = 0;
     int64_t batch_notrim_shape = 0;      // (h, w, sample_ratio, mode) whose sequences once outgrew launches trimmed to the lanes in use
+    int batch_redo = 0;                  // psfm_ctx_set_batch_redo (read from the batch's owner): sequences that leave the fused batch run
+                                         // 0 alone through psfm_connect, 1 together through the frame-mode multi-problem launch chain
+    // the census of the last psfm_connect_batch (psfm_connect_batch_census): sequences that left the fused batch, those that went through
+    // redo_together, and that run's launches / iteration launches / host synchronisations
+    int32_t bt_left = 0, bt_together = 0, bt_fixed = 0, bt_iter = 0, bt_syncs = 0;
     PsfmBuf win_ws;                      // psfm_window_sample / psfm_result_filter workspace
     // psfm_window_sample_batch (psfm_window_batch.hip): the selection of all windows of one call, kept between a plan call and its
     // fill calls.  A buffer of its own: psfm_window_sample and psfm_result_filter may run in between and reuse win_ws.
@@ -463,6 +468,15 @@ psfm_status psfm_launch_flush_batch(const void* tab_dev, int n_seq, int64_t cap_
 psfm_status psfm_launch_batch_set_pc(const void* tab_dev, const int (*v)[4], int n_seq, hipStream_t s);
 size_t psfm_batch_pack_row_bytes(int win);
 psfm_status psfm_launch_batch_pack(const void* tab_dev, const int* lo, int n_seq, int win, char* out_dev, hipStream_t s);
+// the frame-mode multi-problem launch chain (psfm_solver_multi.hip; index rules psfm_batch_chain.h): the per-frame solves of a table
+// of sequences with one grid -- a row from the sequence's track_optimize row, one frame's solves (init launch, paced iteration
+// launches and polls into pinned memory, write-back launch; the census counters are the caller's), what the last poll saw
+size_t psfm_frame_row_bytes(void);
+size_t psfm_frame_poll_bytes(void);
+psfm_status psfm_frame_row_fill(psfm_ctx* c, const PsfmTrackDims& d, const void* seq_opt_row_host, void* row_host, int* n_blocks);
+psfm_status psfm_frame_solve_batch(const void* rows_dev, int grid_x, int n_problems, int f, void* poll_pinned, int32_t* n_fixed,
+                                   int32_t* n_iter, int32_t* n_syncs, hipStream_t s);
+void psfm_frame_poll_read(const void* poll_pinned, int i, int* active, psfm_solve_stats* st, int* n_lanes, int* overflow, int* stall);
 // one segmented finalize for all sequences of a batch (psfm_finalize.hip): ONE host synchronisation, ONE sort.  dims[i] are the
 // sequences' dimensions (same key format); the shared workspace is `own`'s, results land in every context's own res_* buffers
 psfm_status psfm_finalize_batch(psfm_ctx* own, psfm_ctx* const* ctxs, const PsfmTrackDims* dims, int n_seq, hipStream_t s);

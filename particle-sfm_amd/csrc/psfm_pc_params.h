@@ -10,6 +10,7 @@
 #define PC_BLOCK 256
 #include "psfm_pc_resident.h"
 #include "psfm_pc_reduce.h"
+#include "psfm_batch_chain.h"
 #ifndef PC_FUSED_PAIR
 #define PC_FUSED_PAIR false  // ... and the fused solve's: its lanes are neighbours in the image, and the frame kernel spills 7 VGPRs with them
 #endif
@@ -160,12 +161,8 @@ __device__ __forceinline__ bool pc_is_last_block(unsigned* ticket)
 // What changes from one frame to the next in the solver's arguments (frame mode)
 __host__ __device__ inline void pc_params_rebase(PcParams& P, const PsfmSeqStride& st, int64_t occ2_stride, int f)
 {
-    const int64_t df = (int64_t)f - P.frame;
-    P.p0 += df * st.cap; P.x1a += df * st.cap; P.x2a += df * st.cap;
-    P.flow01 += df * st.flow; P.flow12 += df * st.flow; P.flow02 += df * st.flow;
-    P.occ02 += df * occ2_stride;
-    P.frame = f;
-    P.max_birth = f - 1;
+    // (the rule itself is written over any argument block in psfm_batch_chain.h, where the CPU suite compiles and runs it)
+    pc_frame_rebase(P, (long long)st.cap, (long long)st.flow, (long long)occ2_stride, f);
 }
 
 // one sequence's row of the batch table (psfm_solver_batch.hip; filled by psfm_batch_fill_seq_opt)

@@ -295,26 +295,17 @@ static psfm_status qpb_track(void* user, const PsfmQbRun& run)
             QPB_LAUNCH(psfm_qpb_rows_kernel, blocks, dseq, dend, k, back);
             pc_multi_launch_init(drows, grid_x, n_seq, k, s);
             QPB_FIXED(1);
-            pc_multi_launch_iter(drows, grid_x, n_seq, k, 4, s);
-            own->qpb_iter += 4;
-            PSFM_HIP(hipGetLastError());
-            // pc_finish_sync's policy over the batch: poll, and while any problem is left undone another chunk of iterations
-            int launched = 0, chunk = 6;
-            for (;;) {
-                pc_multi_launch_poll(drows, n_seq, k, hs->poll, s);
-                QPB_FIXED(1);
-                PSFM_HIP(hipGetLastError());
-                PSFM_HIP(hipStreamSynchronize(s));
-                own->qpb_syncs += 1;
-                bool undone = false;
-                for (int i = 0; i < n_seq; ++i) undone = undone || (hs->poll[i].n_rows > 0 && !hs->poll[i].C.done);
-                if (!undone) break;
-                if (launched > 2 * 200 + 64) { psfm_set_error(QPB_WHO ": path-consistency solver did not terminate"); return PSFM_ERR_SOLVER; }
-                pc_multi_launch_iter(drows, grid_x, n_seq, k, chunk, s);
-                own->qpb_iter += chunk;
-                launched += chunk;
-                chunk = chunk < 32 ? chunk * 2 : 32;
-            }
+            // pc_finish_sync's policy over the batch (pc_multi_pace): poll, and while any problem is left undone another chunk of iterations
+            const PcPaceCensus census{&own->qpb_fixed, &own->qpb_iter, &own->qpb_syncs};
+            st = pc_multi_pace([&](int n_launches) { pc_multi_launch_iter(drows, grid_x, n_seq, k, n_launches, s); },
+                               [&]() { pc_multi_launch_poll(drows, n_seq, k, hs->poll, s); },
+                               [&]() {
+                                   bool undone = false;
+                                   for (int i = 0; i < n_seq; ++i) undone = undone || (hs->poll[i].n_rows > 0 && !hs->poll[i].C.done);
+                                   return undone;
+                               },
+                               census, s, QPB_WHO);
+            if (st != PSFM_OK) return st;
             pc_multi_launch_writeback(drows, grid_x, n_seq, k, s);
             QPB_FIXED(1);
             QPB_LAUNCH(psfm_qpb_scatter_kernel, blocks, dseq, dend, k, back);

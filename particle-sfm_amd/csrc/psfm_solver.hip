@@ -641,9 +641,7 @@ static int pc_blocks(const psfm_ctx* c, int n_rows_upper)
     static const int limit_env = getenv("PSFM_PC_BLOCKS") ? atoi(getenv("PSFM_PC_BLOCKS")) : 0;
     int limit = limit_env >= 1 && limit_env <= PC_MAX_BLOCKS ? limit_env : PC_CHAIN_BLOCKS;
     if (c->resident_budget > 0 && c->resident_budget < limit) limit = c->resident_budget;
-    int n_blocks = (n_rows_upper + PC_BLOCK - 1) / PC_BLOCK;
-    if (n_blocks > limit) n_blocks = limit;
-    return n_blocks < 1 ? 1 : n_blocks;
+    return pc_frame_blocks(n_rows_upper, limit);      // (clamp(ceil(rows / PC_BLOCK), 1, limit): psfm_batch_chain.h, run by the CPU suite)
 }
 
 // sol_ctrl layout: [PsfmSolveCtrl][ticket u32][zero word used as the `stall` flag of batch solves]

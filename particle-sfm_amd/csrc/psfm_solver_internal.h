@@ -33,6 +33,42 @@ void pc_multi_launch_poll(const PcMultiRow* tab, int n_problems, int k, PcMultiP
 // the statistics of a finished solve from its control block, as psfm_solve_batch reports them
 void pc_multi_stats(const PsfmSolveCtrl* C, psfm_solve_stats* st);
 
+// pc_finish_sync's pacing of a solve, over a table of problems: four iteration launches, one poll into pinned memory and ONE
+// synchronisation; while any problem is left undone another chunk of iteration launches (6, doubling to 32) and another poll; at
+// most 2 * 200 + 64 iterations past the first poll.  iter(n): enqueue n iteration launches; poll(): enqueue the poll; undone(): read
+// what the poll left.  The one statement of the policy for both batch callers (psfm_query_pc_batch.hip, psfm_batch.hip), each with
+// its own census counters.
+struct PcPaceCensus { int32_t* fixed; int32_t* iter; int32_t* syncs; };
+template <class Iter, class Poll, class Undone>
+static inline psfm_status pc_multi_pace(Iter&& iter, Poll&& poll, Undone&& undone, const PcPaceCensus& n, hipStream_t s, const char* who)
+{
+    iter(4);
+    *n.iter += 4;
+    PSFM_HIP(hipGetLastError());
+    int launched = 0, chunk = 6;
+    for (;;) {
+        poll();
+        *n.fixed += 1;
+        PSFM_HIP(hipGetLastError());
+        PSFM_HIP(hipStreamSynchronize(s));
+        *n.syncs += 1;
+        if (!undone()) break;
+        if (launched > 2 * 200 + 64) { psfm_set_error("%s: path-consistency solver did not terminate", who); return PSFM_ERR_SOLVER; }
+        iter(chunk);
+        *n.iter += chunk;
+        launched += chunk;
+        chunk = chunk < 32 ? chunk * 2 : 32;
+    }
+    return PSFM_OK;
+}
+
+// ---- psfm_solver_multi.hip, frame mode: the grid tracker's per-frame solves over a table of sequences (index rules: psfm_batch_chain.h) ----
+// One sequence of the table: the solver arguments of frame 1 in the sequence's OWN context (what PsfmBatchSeqOpt holds for the fused
+// batch kernel), the strides pc_params_rebase turns them into any frame's with, and the single chain's block count for that context.
+struct PcMultiFrameRow { PcParams P; PsfmSeqStride st; int64_t occ2_stride; int n_flows; int n_blocks; };
+// what the frame-mode poll leaves in pinned memory per sequence: the control block of the frame's solve and the sequence's counters
+struct PcMultiFramePoll { PsfmSolveCtrl C; int active; int n_lanes; int overflow; int stall; };
+
 // ---- psfm_solver_fused.hip ----
 psfm_status pc_fused_workspace(psfm_ctx* c, const PsfmTrackDims& d, PcParams& P, int K, hipStream_t s, bool zero_tickets = false);
 psfm_status pc_launch_fused_export(psfm_ctx* c, const PsfmTrackDims& d, PcParams& P, int K, hipStream_t s);

@@ -41,6 +41,7 @@ EXPORTS = [
     "psfm_result_filter_batch", "psfm_traj_to_matches_batch", "psfm_labels_to_matches_batch", "psfm_matches_batch_census", "psfm_labels_sizes",
     "psfm_track_queries_batch", "psfm_query_batch_census",
     "psfm_track_queries_optimize_batch", "psfm_query_pc_batch_census",
+    "psfm_ctx_set_batch_redo", "psfm_connect_batch_census",
 ]
 
 
@@ -105,6 +106,8 @@ def lib():
     L.psfm_connect.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, vp, vp, ctypes.POINTER(TrackInfo), vp]
     L.psfm_connect_batch.argtypes = [ctypes.POINTER(vp), i32, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp),
                                      ctypes.POINTER(i32), i32, i32, f32, i32, ctypes.POINTER(TrackInfo), vp]
+    L.psfm_ctx_set_batch_redo.argtypes = [vp, i32]
+    L.psfm_connect_batch_census.argtypes = [vp] + [ctypes.POINTER(ctypes.c_int32)] * 5
     L.psfm_track_queries.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, i64, ctypes.POINTER(TrackInfo), vp]
     L.psfm_track_queries_optimize.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, i64, ctypes.POINTER(TrackInfo), vp]
     L.psfm_track_queries_batch.argtypes = [ctypes.POINTER(vp), i32, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp),
@@ -228,6 +231,7 @@ class Context:
         check(lib().psfm_ctx_create(int(device), ctypes.byref(self._h)))
         self.device = int(device)
         self.resident_budget = 0           # (what set_resident_budget was last given)
+        self.batch_redo = 0                # (what set_batch_redo was last given)
 
     @property
     def handle(self):
@@ -250,6 +254,25 @@ class Context:
         """track_optimize: 0 adaptive (fused solve, launch chain for windows whose solves reject steps), 1 launch chain,
         2 fused solve; k = trust-region iterations per fused launch (0: adaptive)."""
         check(lib().psfm_ctx_set_solver(self._h, int(mode), int(k)))
+
+    BATCH_REDO = {"alone": 0, "together": 1}
+
+    def set_batch_redo(self, mode):
+        """psfm_connect_batch with this context as its first: how the sequences that leave the fused batch (their solves reject steps)
+        are run again -- "alone" / 0: each through psfm_connect (default); "together" / 1: all of them through one set of launches, their
+        solves as the frame-mode multi-problem launch chain (info.chain_mode 8)."""
+        mode = self.BATCH_REDO.get(mode, mode)
+        check(lib().psfm_ctx_set_batch_redo(self._h, int(mode)))
+        self.batch_redo = int(mode)
+
+    def connect_batch_census(self):
+        """The last psfm_connect_batch call that had this context as its first: sequences that left the fused batch, those that were
+        redone together, and of that redo the launches that do not depend on how the solves went, the trust-region iteration launches
+        and the host synchronisations.  Per frame the fixed launches are three whatever the number of sequences; polls, iteration launches
+        and synchronisations follow the slowest solve of the frame in the table and do not grow beyond its need."""
+        v = [ctypes.c_int32() for _ in range(5)]
+        check(lib().psfm_connect_batch_census(self._h, *[ctypes.byref(x) for x in v]))
+        return dict(zip(("n_left", "n_together", "launches_fixed", "launches_iter", "host_syncs"), (int(x.value) for x in v)))
 
     def set_resident_budget(self, blocks):
         """> 0: this context's resident solves (flows whose solves reject steps) use at most `blocks` blocks and may run beside other

@@ -25,9 +25,9 @@ BATCH_BYTES = 48 << 30         # flow stacks of one group resident in HBM before
 
 
 def _connect_batch_to_disk(flow_dirs, traj_dirs, sample_ratio, flow_check_thres, traj_min_len, skip_path_consistency, skip_exists, layout,
-                           motion_boundary=False, mb_thres=0.02, mb_engine=None):
+                           motion_boundary=False, mb_thres=0.02, mb_engine=None, redo=None):
     """main_connect_point_trajectories.py:27-62 for a group of sequences through psfm_connect_batch: ingest all, ONE batched
-    compute call per frame size, then filter + save each from its own context.  motion_boundary / mb_thres / mb_engine: as in run_connect_batch
+    compute call per frame size, then filter + save each from its own context.  motion_boundary / mb_thres / mb_engine / redo: as in run_connect_batch
     (the PSFM_MOTION_BOUNDARY switch of the one-sequence entry point holds here too)."""
     import os
     from .utils import load_flows_device
@@ -39,7 +39,7 @@ def _connect_batch_to_disk(flow_dirs, traj_dirs, sample_ratio, flow_check_thres,
 
     def flush(group):
         ctxs, infos = run_connect_batch([sq for _, sq in group], flow_check_thres, sample_ratio, motion_boundary=motion_boundary, mb_thres=mb_thres,
-                                        mb_engine=mb_engine)
+                                        mb_engine=mb_engine, redo=redo)
         for (td, _), ctx, info in zip(group, ctxs, infos):
             ts = result_to_trajectory_set(ctx, info, traj_min_len, reuse_pinned=True)
             save_track_npy(os.path.join(td, "track.npy"), ts, layout=layout)
@@ -75,8 +75,10 @@ def _connect_batch_to_disk(flow_dirs, traj_dirs, sample_ratio, flow_check_thres,
 
 def connect_sequences(flow_dirs, traj_dirs, sample_ratio=2, flow_check_thres=1.0, traj_min_len=3,
                       skip_path_consistency=False, skip_exists=False, concurrency=2, rank=None, world=None, layout="csr", batch=1,
-                      motion_boundary=False, mb_thres=0.02, mb_engine=None):
+                      motion_boundary=False, mb_thres=0.02, mb_engine=None, redo=None):
     """main_connect_point_trajectories for a list of sequences; returns the indices this rank processed.
+    redo (batch > 1, path consistency): how sequences that leave a batch are run again -- "alone", "together" or None (as
+    run_connect_batch: the contexts' setting, "alone" by default).
     layout: pickle state of the track.npy files -- "csr" (default here: the batch driver is this package's own entry
     point and its files are read back through this package) or "reference" (files for an unmodified checkout).
     batch > 1: every worker takes up to `batch` sequences at a time through psfm_connect_batch (small frames: see above).
@@ -125,7 +127,7 @@ def connect_sequences(flow_dirs, traj_dirs, sample_ratio=2, flow_check_thres=1.0
                     if batch > 1:
                         _connect_batch_to_disk([flow_dirs[k] for k in ks], [traj_dirs[k] for k in ks], sample_ratio, flow_check_thres,
                                                traj_min_len, skip_path_consistency, skip_exists, layout, motion_boundary=motion_boundary,
-                                               mb_thres=mb_thres, mb_engine=mb_engine)
+                                               mb_thres=mb_thres, mb_engine=mb_engine, redo=redo)
                         continue
                     main_connect_point_trajectories(flow_dirs[k], traj_dirs[k], sample_ratio=sample_ratio,
                                                     flow_check_thres=flow_check_thres, traj_min_len=traj_min_len,

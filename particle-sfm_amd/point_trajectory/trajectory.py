@@ -367,7 +367,7 @@ def run_connect(flows_f, flows_b, flows_f2, flows_b2, thres, sample_ratio, retur
 MB_ENGINE_DEFAULT = "batch"
 
 
-def run_connect_batch(seqs, thres, sample_ratio, motion_boundary=False, mb_thres=0.02, mb_engine=None):
+def run_connect_batch(seqs, thres, sample_ratio, motion_boundary=False, mb_thres=0.02, mb_engine=None, redo=None):
     """psfm_connect_batch: flow_check + track / track_optimize for a BATCH of same-shape sequences (the directory of sequences the
     reference's driver walks, run_particlesfm.py:168-176) with every frame launch covering the whole batch.
     seqs: list of (flows_f, flows_b, flows_f2 | None, flows_b2 | None) device tensors (n_i,H,W,2) -- all with stride-2 stacks or
@@ -375,11 +375,17 @@ def run_connect_batch(seqs, thres, sample_ratio, motion_boundary=False, mb_thres
     `result_to_trajectory_set(ctx, info)`) until the calling thread's next batch.
     motion_boundary: tracks also die on motion boundaries of threshold mb_thres (one value, or one per sequence).  mb_engine "batch":
     the option is set on every batch context for the duration of the call and the batched launches form the verdict; "loop": the
-    sequences go through run_connect one after the other, each on its own context; None: MB_ENGINE_DEFAULT.  Same results."""
+    sequences go through run_connect one after the other, each on its own context; None: MB_ENGINE_DEFAULT.  Same results.
+    redo: how the sequences that leave the fused batch (path consistency on flows whose solves reject steps) are run again -- "alone":
+    each through psfm_connect; "together": all of them through one set of launches (Context.set_batch_redo; info.chain_mode 8, census
+    in ctxs[0].connect_batch_census()); None: as the batch's first context is set (default "alone"; PSFM_BATCH_REDO=together|alone
+    overrides all of it, for measurements).  A string sets the option for the duration of the call."""
     import torch
     n_seq = len(seqs)
     if n_seq < 1:
         return [], []
+    if redo not in (None, "alone", "together"):
+        raise ValueError("connect_batch: redo must be 'alone', 'together' or None")
     mb_list = None
     if motion_boundary:
         mb_list = [float(mb_thres)] * n_seq if np.isscalar(mb_thres) else [float(t) for t in mb_thres]
@@ -419,7 +425,10 @@ def run_connect_batch(seqs, thres, sample_ratio, motion_boundary=False, mb_thres
     infos = (_hip.TrackInfo * n_seq)()
     cap_key = ("batch", H, W, int(sample_ratio), opt)
     lane_f, traj_f = _capacity_of(ctxs[0], cap_key)
+    redo_before = ctxs[0].batch_redo
     try:
+        if redo is not None:
+            ctxs[0].set_batch_redo(redo)
         if mb_list is not None:
             for c, t in zip(ctxs, mb_list):
                 c.set_motion_boundary(True, t)
@@ -436,6 +445,8 @@ def run_connect_batch(seqs, thres, sample_ratio, motion_boundary=False, mb_thres
         if mb_list is not None:      # (the option is per context and the thread's batch contexts are reused: off again, whatever happened)
             for c in ctxs:
                 c.set_motion_boundary(False)
+        if redo is not None:
+            ctxs[0].set_batch_redo(redo_before)
     _hip.check(st)
     return ctxs, [infos[i] for i in range(n_seq)]
 
