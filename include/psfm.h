@@ -421,8 +421,8 @@ psfm_status psfm_track_queries_optimize_batch(psfm_ctx* const* ctxs, int n_seq, 
 psfm_status psfm_query_pc_batch_census(psfm_ctx* ctx, int32_t* launches_fixed, int32_t* launches_iter, int32_t* host_syncs);
 
 /* The loop of the reference's driver over a directory of sequences (run_particlesfm.py:168-176 -> connect_point_trajectory ->
- * main_connect_point_trajectories.py:36-53 per sequence) for n_seq sequences of the SAME frame size and sample ratio (any
- * lengths) in ONE call: psfm_connect for every one of them, with every frame launch covering the whole batch (block (x, y) = tile
+ * main_connect_point_trajectories.py:36-53 per sequence) for n_seq sequences of one sample ratio (any lengths; one frame size h x w,
+ * or with h = w = 0 a frame size per sequence, see below) in ONE call: psfm_connect for every one of them, with every frame launch covering the whole batch (block (x, y) = tile
  * x of sequence y).  A frame of a small sequence -- DAVIS, Sintel, ScanNet sizes -- is one dependent chain of memory round trips on
  * a few hundred of the device's block slots; a batch fills them.  One host synchronisation per window of 16 frames and one
  * segmented finalize (one sort) for all sequences.
@@ -464,13 +464,27 @@ psfm_status psfm_query_pc_batch_census(psfm_ctx* ctx, int32_t* launches_fixed, i
  * sequence whose solve is the slowest of a frame adds a chunk of iteration launches and a poll there.
  * The joint redo files its solves in each context's adaptive policy (psfm_ctx_set_solver mode 0: launch chain or fused solve next,
  * iterations per fused launch), as the checkpoints of psfm_connect do for a sequence redone alone, over the whole sequence instead
- * of its last window: what a context starts its next call with may differ between the two routes. */
+ * of its last window: what a context starts its next call with may differ between the two routes.
+ * Sequences of different frame sizes: h = w = 0, and every ctxs[i] carries the frame size of sequence i (psfm_ctx_set_frame_size):
+ * flows_f[i] is (n_flows[i],H_i,W_i,2) and so on.  One sample_ratio, one thres, stride-2 stacks for all or none, as above; every
+ * result, info->chain_mode and the census are what the call gives the sequences grouped by size (track mode: the same bytes; path
+ * consistency: as between two runs).  Exactly one of h, w being 0 is PSFM_ERR_ARG, and so is a context without a frame size (the
+ * lowest such sequence is named).  With h > 0 and w > 0 the contexts' stored sizes are ignored; with h = w = 0 and all stored sizes
+ * equal the call is the one with that h, w.  The frame launches read every dimension from the sequence's row and keep blockIdx.y =
+ * sequence (a block beyond a small sequence's lanes leaves at once); flow_check and the kill maps run over a grid flattened over the
+ * sequences; the segmented finalize sorts with the key fields of the widest grid and the longest sequence, which leaves every
+ * sequence's order -- its ids -- what it is alone.  When one stack cannot take the 16-byte-load flow_check (fewer than 1024 pixels, an
+ * odd pixel count, a misaligned stack) the maps of all stacks are made up front, stack by stack. */
 psfm_status psfm_connect_batch(psfm_ctx* const* ctxs, int n_seq, const float* const* flows_f, const float* const* flows_b,
                                const float* const* flows_f2, const float* const* flows_b2, const int* n_flows, int h, int w,
                                float thres, int sample_ratio, psfm_track_info* infos_host, void* stream);
 /* mode 0: sequences that leave the fused batch run alone through psfm_connect (default); 1: together (see above).  Read from ctxs[0]
  * of a psfm_connect_batch call.  Any other value: PSFM_ERR_ARG. */
 psfm_status psfm_ctx_set_batch_redo(psfm_ctx* ctx, int mode);
+/* The frame size of the sequence this context holds in a psfm_connect_batch call with h = w = 0.  (0, 0) clears it; anything else must
+ * be a frame size the entry points take (h, w >= 2, h w < 2^29), else PSFM_ERR_ARG and the stored size stays.  No other entry point
+ * reads it. */
+psfm_status psfm_ctx_set_frame_size(psfm_ctx* ctx, int h, int w);
 psfm_status psfm_connect_batch_census(psfm_ctx* ctx0, int32_t* n_left, int32_t* n_together, int32_t* launches_fixed,
                                       int32_t* launches_iter, int32_t* host_syncs);
 

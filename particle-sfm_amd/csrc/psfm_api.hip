@@ -240,6 +240,18 @@ extern "C" psfm_status psfm_ctx_set_batch_redo(psfm_ctx* c, int mode)
     return PSFM_OK;
 }
 
+extern "C" psfm_status psfm_ctx_set_frame_size(psfm_ctx* c, int h, int w)
+{
+    if (!c) { psfm_set_error("ctx is NULL"); return PSFM_ERR_ARG; }
+    if (!(h == 0 && w == 0) && !psfm_frame_ok(h, w)) {
+        psfm_set_error("psfm_ctx_set_frame_size: bad frame size (h=%d w=%d; 0, 0 clears it)", h, w);
+        return PSFM_ERR_ARG;
+    }
+    c->batch_h = h;
+    c->batch_w = w;
+    return PSFM_OK;
+}
+
 extern "C" psfm_status psfm_solver_counters(psfm_ctx* c, int64_t* fused, int64_t* fused_redone, int64_t* chain, int32_t* k_now)
 {
     if (!c) { psfm_set_error("ctx is NULL"); return PSFM_ERR_ARG; }

@@ -1,4 +1,4 @@
-// psfm_batch.hip -- psfm_connect_batch: B same-shape sequences through ONE set of launches.
+// psfm_batch.hip -- psfm_connect_batch: B sequences (of one frame size, or each of its own) through ONE set of launches.
 //
 // The reference's driver walks a directory of sequences (run_particlesfm.py:168-176: connect_point_trajectory per sequence), and the
 // sequences real data has are small: DAVIS 480x854 at sample_ratio 4 is 25 k grid points, Sintel 436x1024 at 2 is 112 k, ScanNet
@@ -22,6 +22,10 @@
 //   * psfm_ctx_set_motion_boundary on EVERY context of the batch: the frame launches are the MB forms of the two kernels
 //     (psfm_motion_boundary.hip, psfm_solver_batch_mb.hip) and sample every sequence's kill maps (c->kill), built by ONE launch per
 //     flow_check chunk for all sequences (psfm_kill_map_batch_kernel); contexts that disagree are refused.
+//   * h = w = 0: every context carries its sequence's frame size (psfm_ctx_set_frame_size).  All equal: the run with that size.  Else
+//     every sequence has its own dimensions wherever the run sizes, fills or launches per sequence (the rows already hold them);
+//     flow_check and the kill maps run over a grid flattened over the sequences (psfm_batch_shapes.h); the records of all sequences
+//     get the index bits of the widest grid, so that the one finalize sorts one key format (tests/test_gpu_batch_shapes.py).
 // Results are those of psfm_connect, sequence by sequence (tests/test_gpu_batch.py: bit-identical to the oracle's).
 #include <string.h>
 #include <stdlib.h>
@@ -34,6 +38,9 @@
 #include "psfm_chain_step.h"
 #include "psfm_solve_policy.h"
 #include "psfm_batch_chain.h"
+#include "psfm_batch_shapes.h"
+
+static_assert(PSFM_BS_MAX == PSFM_BATCH_MAX, "one bound for every batch entry point");
 
 namespace {
 struct SeqState {
@@ -69,13 +76,15 @@ static psfm_status batch_host_staging(psfm_ctx* own, size_t need)
 
 static psfm_status batch_run(psfm_ctx* const* ctxs, int n_seq, const float* const* flows_f, const float* const* flows_b,
                              const float* const* flows_f2, const float* const* flows_b2, const int* n_flows, int h, int w,
-                             float thres, int ratio, psfm_track_info* infos, void* stream, bool trim, bool* grid_too_small);
+                             const int* hs, const int* ws, float thres, int ratio, psfm_track_info* infos, void* stream, bool trim,
+                             bool* grid_too_small);
 
 extern "C" psfm_status psfm_connect_batch(psfm_ctx* const* ctxs, int n_seq, const float* const* flows_f, const float* const* flows_b,
                                           const float* const* flows_f2, const float* const* flows_b2, const int* n_flows, int h, int w,
                                           float thres, int ratio, psfm_track_info* infos, void* stream)
 {
-    if (!ctxs || n_seq < 1 || n_seq > PSFM_BATCH_MAX || !flows_f || !flows_b || !n_flows || !psfm_frame_ok(h, w) || ratio < 1 || ratio > 64 ||
+    const bool per_ctx = h == 0 && w == 0;      // every context carries its sequence's frame size (psfm_ctx_set_frame_size)
+    if (!ctxs || n_seq < 1 || n_seq > PSFM_BATCH_MAX || !flows_f || !flows_b || !n_flows || (!per_ctx && !psfm_frame_ok(h, w)) || ratio < 1 || ratio > 64 ||
         ((flows_f2 == nullptr) != (flows_b2 == nullptr))) {
         psfm_set_error("psfm_connect_batch: bad argument (n_seq=%d of at most %d, h=%d w=%d sample_ratio=%d)", n_seq, PSFM_BATCH_MAX, h, w, ratio);
         return PSFM_ERR_ARG;
@@ -95,6 +104,24 @@ extern "C" psfm_status psfm_connect_batch(psfm_ctx* const* ctxs, int n_seq, cons
             psfm_set_error("psfm_connect_batch: bad sequence %d (n_flows=%d)", i, n_flows[i]);
             return PSFM_ERR_ARG;
         }
+    }
+    // h = w = 0: the frame sizes are the contexts'.  All equal: the call with that size; else hs / ws go with the run, and what is
+    // remembered per shape below is remembered for the largest frame of the batch.
+    int hsv[PSFM_BATCH_MAX], wsv[PSFM_BATCH_MAX];
+    const int* hs = nullptr;
+    const int* ws = nullptr;
+    if (per_ctx) {
+        bool same = true;
+        for (int i = 0; i < n_seq; ++i) {
+            if (!psfm_frame_ok(ctxs[i]->batch_h, ctxs[i]->batch_w)) {
+                psfm_set_error("psfm_connect_batch: h = w = 0 and context %d has no frame size (psfm_ctx_set_frame_size)", i);
+                return PSFM_ERR_ARG;
+            }
+            hsv[i] = ctxs[i]->batch_h; wsv[i] = ctxs[i]->batch_w;
+            same = same && hsv[i] == hsv[0] && wsv[i] == wsv[0];
+            if (i == 0 || (int64_t)hsv[i] * wsv[i] > (int64_t)h * w) { h = hsv[i]; w = wsv[i]; }
+        }
+        if (!same) { hs = hsv; ws = wsv; }
     }
     // The frame launches cover the lanes a sequence can be expected to use (its grid + 1/8), not its whole lane table (2 x the grid by
     // default): a block beyond the lanes in use leaves at once, but it still has to be dispatched -- half of the blocks of every launch
@@ -117,11 +144,11 @@ extern "C" psfm_status psfm_connect_batch(psfm_ctx* const* ctxs, int n_seq, cons
     };
     psfm_status rc = PSFM_ERR_HIP;
     try {
-        rc = batch_run(ctxs, n_seq, flows_f, flows_b, flows_f2, flows_b2, n_flows, h, w, thres, ratio, infos, stream, trim, &too_small);
+        rc = batch_run(ctxs, n_seq, flows_f, flows_b, flows_f2, flows_b2, n_flows, h, w, hs, ws, thres, ratio, infos, stream, trim, &too_small);
         if (rc != PSFM_OK) quiesce();
         if (rc == PSFM_ERR_CAPACITY && too_small) {
             own0->batch_notrim_shape = shape_key;
-            rc = batch_run(ctxs, n_seq, flows_f, flows_b, flows_f2, flows_b2, n_flows, h, w, thres, ratio, infos, stream, false, &too_small);
+            rc = batch_run(ctxs, n_seq, flows_f, flows_b, flows_f2, flows_b2, n_flows, h, w, hs, ws, thres, ratio, infos, stream, false, &too_small);
             if (rc != PSFM_OK) quiesce();
         }
     } catch (const std::exception& e) {      // (std::thread / std::vector: nothing may unwind through the extern "C" boundary)
@@ -138,13 +165,18 @@ struct BatchRun {
     psfm_ctx* const* ctxs; int B;
     const float* const* flows_f; const float* const* flows_b; const float* const* flows_f2; const float* const* flows_b2;
     const int* n_flows;
-    int h, w; float thres; int ratio;
+    int h, w;                    // the frame size of all sequences; hs != NULL: of the largest one
+    const int* hs; const int* ws;      // NULL, or the frame size of every sequence (a batch of several sizes)
+    float thres; int ratio;
     hipStream_t s;
     bool trim; bool* grid_too_small;
     psfm_ctx* own;               // the batch's owner: shared workspaces, side stream, profiler
     bool optimize, mb;           // mb: psfm_ctx_set_motion_boundary, on in every context of the batch: the frame launches sample kill maps
-    int64_t P;
     PsfmOccPipeline fc;          // the flow_check pipeline of all sequences, on the owner's side stream
+    bool shapes() const { return hs != nullptr; }
+    int fh(int i) const { return hs ? hs[i] : h; }
+    int fw(int i) const { return ws ? ws[i] : w; }
+    int64_t fP(int i) const { return (int64_t)fh(i) * fw(i); }      // pixels of a map of sequence i: the pitch of its map buffers
     std::vector<SeqState> S;
     std::vector<PsfmTrackDims> D;
     int n_max = 0;
@@ -168,25 +200,33 @@ struct BatchRun {
     psfm_status redo_together(const std::vector<int>& redo, psfm_track_info* infos);
 };
 
-// ---- dimensions (one key format for the whole batch: the time bits of its longest sequence), workspaces ----
+// ---- dimensions (one key format for the whole batch: the time bits of its longest sequence, the index bits of its widest grid --
+// psfm_bs_common_key -- written into every sequence's dimensions before anything is sized or filled from them), workspaces ----
 psfm_status BatchRun::prepare()
 {
     psfm_status st;
     S.resize((size_t)B); D.resize((size_t)B);
     for (int i = 0; i < B; ++i) n_max = n_flows[i] > n_max ? n_flows[i] : n_max;
-    int tbits = 1;
-    while ((1ll << tbits) < (long long)n_max + 2) ++tbits;
+    int sb[PSFM_BATCH_MAX];
+    for (int i = 0; i < B; ++i) {
+        psfm_shard_abandon(ctxs[i]);
+        if ((st = psfm_track_dims(ctxs[i], n_flows[i], fh(i), fw(i), ratio, -1, D[i])) != PSFM_OK) return st;
+        sb[i] = D[i].shift_b;
+    }
+    // (sequences of one frame size have one grid: their index bits are the common ones already)
+    const PsfmBsKeyFmt key = psfm_bs_common_key(sb, n_flows, B);
+    const int tbits = key.tbits;
     for (int i = 0; i < B; ++i) {
         psfm_ctx* c = ctxs[i];
-        psfm_shard_abandon(c);
-        if ((st = psfm_track_dims(c, n_flows[i], h, w, ratio, -1, D[i])) != PSFM_OK) return st;
-        D[i].shift_d = D[i].shift_b + tbits;
+        const size_t P = (size_t)fP(i);
+        D[i].shift_b = key.shift_b;
+        D[i].shift_d = key.shift_d;
         if (D[i].shift_d + tbits > 63) { psfm_set_error("psfm_connect_batch: key does not fit 64 bits"); return PSFM_ERR_ARG; }
         if ((st = psfm_track_alloc(c, D[i])) != PSFM_OK) return st;
-        if ((st = c->occ_own.ensure((size_t)P * (size_t)n_flows[i])) != PSFM_OK) return st;
-        if (mb && (st = c->kill.ensure((size_t)P * (size_t)n_flows[i])) != PSFM_OK) return st;
+        if ((st = c->occ_own.ensure(P * (size_t)n_flows[i])) != PSFM_OK) return st;
+        if (mb && (st = c->kill.ensure(P * (size_t)n_flows[i])) != PSFM_OK) return st;
         if (optimize) {
-            if ((st = c->occ2_own.ensure((size_t)P * (size_t)(n_flows[i] > 1 ? n_flows[i] - 1 : 1))) != PSFM_OK) return st;
+            if ((st = c->occ2_own.ensure(P * (size_t)(n_flows[i] > 1 ? n_flows[i] - 1 : 1))) != PSFM_OK) return st;
             if ((st = psfm_solve_prepare(c, D[i], s)) != PSFM_OK) return st;
         }
         psfm_call_begin(c, n_flows[i], false);
@@ -210,6 +250,9 @@ psfm_status BatchRun::prepare()
 // Option on: every stride-1 chunk is followed, on the side stream, by the kill-map launch of the same frames of all sequences
 // (psfm_kill_map_batch_kernel reads the occlusion bytes of those frames only) and the chunk's event is recorded behind it, so
 // that waiting for a chunk is waiting for its kill maps; up front, the kill maps follow their stack's flow_check.
+// Several frame sizes: the same pipeline with the two launches over a grid flattened over the sequences
+// (psfm_flow_check_x2v_shapes_kernel, psfm_kill_map_shapes_kernel; psfm_batch_shapes.h); the rule for the up-front path is taken
+// per batch -- ONE stack that fails the test for its own frame size sends all of them there (the per-stack launches take any size).
 psfm_status BatchRun::flow_check()
 {
     psfm_status st;
@@ -217,8 +260,8 @@ psfm_status BatchRun::flow_check()
     int fc_chunk = fc_env >= 0 ? fc_env : (optimize ? 6 : 8);
     for (int i = 0; i < B && fc_chunk > 0; ++i) {
         if (no_maps(i)) continue;
-        if (!psfm_flow_check_batch_ok(h, w, flows_f[i], flows_b[i], ctxs[i]->occ_own.p)) fc_chunk = 0;
-        if (optimize && n_flows[i] > 1 && !psfm_flow_check_batch_ok(h, w, flows_f2[i], flows_b2[i], ctxs[i]->occ2_own.p)) fc_chunk = 0;
+        if (!psfm_flow_check_batch_ok(fh(i), fw(i), flows_f[i], flows_b[i], ctxs[i]->occ_own.p)) fc_chunk = 0;
+        if (optimize && n_flows[i] > 1 && !psfm_flow_check_batch_ok(fh(i), fw(i), flows_f2[i], flows_b2[i], ctxs[i]->occ2_own.p)) fc_chunk = 0;
     }
     fc.chunk = fc_chunk;      // chunk c of the stride-1 / stride-2 maps: pairs [c * fc_chunk, (c + 1) * fc_chunk)
     own->prof.begin(PSFM_PROF_FLOW_CHECK, s);
@@ -226,21 +269,29 @@ psfm_status BatchRun::flow_check()
         for (int i = 0; i < B; ++i) {
             if (no_maps(i)) continue;
             psfm_ctx* c = ctxs[i];
-            if ((st = psfm_launch_flow_check(flows_f[i], flows_b[i], n_flows[i], h, w, thres, c->occ_own.as<uint8_t>(), nullptr, s)) != PSFM_OK) return st;
+            const int hi = fh(i), wi = fw(i);
+            if ((st = psfm_launch_flow_check(flows_f[i], flows_b[i], n_flows[i], hi, wi, thres, c->occ_own.as<uint8_t>(), nullptr, s)) != PSFM_OK) return st;
             if (optimize && n_flows[i] > 1 &&
-                (st = psfm_launch_flow_check(flows_f2[i], flows_b2[i], n_flows[i] - 1, h, w, thres, c->occ2_own.as<uint8_t>(), nullptr, s)) != PSFM_OK) return st;
-            if (mb && (st = psfm_launch_motion_boundary(flows_f[i], c->occ_own.as<uint8_t>(), n_flows[i], h, w, c->mb_thres, c->kill.as<uint8_t>(), s)) != PSFM_OK)
+                (st = psfm_launch_flow_check(flows_f2[i], flows_b2[i], n_flows[i] - 1, hi, wi, thres, c->occ2_own.as<uint8_t>(), nullptr, s)) != PSFM_OK) return st;
+            if (mb && (st = psfm_launch_motion_boundary(flows_f[i], c->occ_own.as<uint8_t>(), n_flows[i], hi, wi, c->mb_thres, c->kill.as<uint8_t>(), s)) != PSFM_OK)
                 return st;
         }
         own->prof.end(s);
         return PSFM_OK;
     }
-    const size_t fc_bytes = sizeof(PsfmFcSeq) * (size_t)B * 2;
-    const size_t fbytes = fc_bytes + (mb ? sizeof(PsfmKmSeq) * (size_t)B : 0);      // (rows of 32 bytes, both)
+    // (several frame sizes: the stacks are described here and their rows -- frame, chunks, place in the flattened grid,
+    // psfm_batch_shapes.h -- are what is uploaded; rows of 80 bytes)
+    const size_t fc_row = shapes() ? sizeof(PsfmFcShapeRow) : sizeof(PsfmFcSeq), km_row = shapes() ? sizeof(PsfmKmShapeRow) : sizeof(PsfmKmSeq);
+    const size_t fc_bytes = fc_row * (size_t)B * 2;
+    const size_t row_bytes = fc_bytes + (mb ? km_row * (size_t)B : 0);    // (rows of 32 bytes, both)
+    // (... and behind the rows the three inclusive block prefixes, 64 entries each: stride-1 / stride-2 flow_check, kill maps)
+    const size_t fbytes = row_bytes + (shapes() ? 3 * PSFM_BS_MAX * sizeof(int) : 0);
     if ((st = batch_host_staging2(own, fbytes)) != PSFM_OK) return st;
     if ((st = own->batch_fc.ensure(fbytes)) != PSFM_OK) return st;
-    PsfmFcSeq* hfc = (PsfmFcSeq*)own->host_batch2;
-    PsfmKmSeq* hkm = (PsfmKmSeq*)((char*)own->host_batch2 + fc_bytes);
+    PsfmFcSeq fc_seq[2 * PSFM_BATCH_MAX];
+    PsfmKmSeq km_seq[PSFM_BATCH_MAX];
+    PsfmFcSeq* hfc = shapes() ? fc_seq : (PsfmFcSeq*)own->host_batch2;
+    PsfmKmSeq* hkm = shapes() ? km_seq : (PsfmKmSeq*)((char*)own->host_batch2 + fc_bytes);
     for (int i = 0; i < B; ++i) {
         psfm_ctx* c = ctxs[i];
         hfc[i].ff = flows_f[i]; hfc[i].fb = flows_b[i]; hfc[i].occ = c->occ_own.as<uint8_t>(); hfc[i].n_pairs = no_maps(i) ? 0 : n_flows[i]; hfc[i].pad = 0;
@@ -252,7 +303,22 @@ psfm_status BatchRun::flow_check()
             hkm[i].n = hfc[i].n_pairs; hkm[i].thres = c->mb_thres;
         }
     }
-    PSFM_HIP(hipMemcpyAsync(own->batch_fc.p, hfc, fbytes, hipMemcpyHostToDevice, s));
+    int blocks_fc[2] = {0, 0}, blocks_km = 0;      // several frame sizes: gridDim.x of the stride-1 / stride-2 flow_check, of the kill maps
+    if (shapes()) {
+        PsfmFcShapeRow* rfc = (PsfmFcShapeRow*)own->host_batch2;
+        PsfmKmShapeRow* rkm = (PsfmKmShapeRow*)((char*)own->host_batch2 + fc_bytes);
+        for (int i = 0; i < B; ++i) {
+            psfm_fc_shape_row(hfc[i], fh(i), fw(i), &rfc[i]);
+            psfm_fc_shape_row(hfc[B + i], fh(i), fw(i), &rfc[B + i]);
+            if (mb) psfm_km_shape_row(hkm[i], fh(i), fw(i), &rkm[i]);
+        }
+        int* ends = (int*)((char*)own->host_batch2 + row_bytes);
+        PsfmKmShapeRow none[1];
+        blocks_fc[0] = psfm_bs_fc_prefix(rfc, B, ends);
+        blocks_fc[1] = psfm_bs_fc_prefix(rfc + B, B, ends + PSFM_BS_MAX);
+        blocks_km = psfm_bs_km_prefix(mb ? rkm : none, mb ? B : 0, ends + 2 * PSFM_BS_MAX);
+    }
+    PSFM_HIP(hipMemcpyAsync(own->batch_fc.p, own->host_batch2, fbytes, hipMemcpyHostToDevice, s));
     if (!own->side_stream) PSFM_HIP(hipStreamCreateWithFlags(&own->side_stream, hipStreamNonBlocking));
     hipStream_t side = own->side_stream;
     fc.start = own->prof.get();      // the side stream starts behind whatever the caller enqueued on `stream` (the inputs, the table)
@@ -260,17 +326,26 @@ psfm_status BatchRun::flow_check()
     PSFM_HIP(hipStreamWaitEvent(side, fc.start, 0));
     const PsfmFcSeq* dfc = own->batch_fc.as<PsfmFcSeq>();
     const PsfmKmSeq* dkm = (const PsfmKmSeq*)((const char*)own->batch_fc.p + fc_bytes);
+    const PsfmFcShapeRow* dfs = own->batch_fc.as<PsfmFcShapeRow>();
+    const PsfmKmShapeRow* dks = (const PsfmKmShapeRow*)((const char*)own->batch_fc.p + fc_bytes);
+    const int* dends = (const int*)((const char*)own->batch_fc.p + row_bytes);
+    // one launch for pairs [p0, p0 + np) of the stride-1 (s2 = 0) / stride-2 stacks of all sequences
+    auto launch_fc = [&](int s2, int p0, int np) {
+        if (shapes()) return psfm_launch_flow_check_shapes(dfs + s2 * B, dends + s2 * PSFM_BS_MAX, blocks_fc[s2], p0, np, thres, side);
+        return psfm_launch_flow_check_batch(dfc + s2 * B, B, p0, np, h, w, thres, side);
+    };
     for (int p0 = 0; p0 < n_max; p0 += fc_chunk) {
         const int np = n_max - p0 < fc_chunk ? n_max - p0 : fc_chunk;
-        if ((st = psfm_launch_flow_check_batch(dfc, B, p0, np, h, w, thres, side)) != PSFM_OK) return st;
+        if ((st = launch_fc(0, p0, np)) != PSFM_OK) return st;
         // (the stacks passed psfm_flow_check_batch_ok: P even, flows 16-byte aligned -- the four-pixels-per-lane form)
-        if (mb && (st = psfm_launch_kill_map_batch(dkm, B, p0, np, h, w, true, side)) != PSFM_OK) return st;
+        if (mb && (st = shapes() ? psfm_launch_kill_map_shapes(dks, dends + 2 * PSFM_BS_MAX, blocks_km, p0, np, side)
+                                 : psfm_launch_kill_map_batch(dkm, B, p0, np, h, w, true, side)) != PSFM_OK) return st;
         hipEvent_t e = own->prof.get();
         fc.ready.push_back(e);
         PSFM_HIP(hipEventRecord(e, side));
         if (optimize && p0 < n_max - 1) {     // the stride-2 maps of the same time range follow their stride-1 chunk
             const int np2 = n_max - 1 - p0 < fc_chunk ? n_max - 1 - p0 : fc_chunk;
-            if ((st = psfm_launch_flow_check_batch(dfc + B, B, p0, np2, h, w, thres, side)) != PSFM_OK) return st;
+            if ((st = launch_fc(1, p0, np2)) != PSFM_OK) return st;
             hipEvent_t e2 = own->prof.get();
             fc.ready_s2.push_back(e2);
             PSFM_HIP(hipEventRecord(e2, side));
@@ -301,11 +376,11 @@ psfm_status BatchRun::tables()
         // (a sequence that has left the batch keeps a row -- blockIdx.y indexes the table -- with no frames to run)
         // (option on: the chain step's mask bytes are the sequence's kill maps; the caller's / the solve's occlusion maps stay 0/1)
         const uint8_t* masks = mb ? c->kill.as<uint8_t>() : c->occ_own.as<uint8_t>();
-        psfm_batch_fill_seq(c, D[i], flows_f[i], masks, P, &htab[i]);
+        psfm_batch_fill_seq(c, D[i], flows_f[i], masks, fP(i), &htab[i]);
         if (S[i].dropped) htab[i].n_flows = 0;
         if (optimize) {
             const float* f2 = n_flows[i] > 1 ? flows_f2[i] : flows_f[i];      // (a one-pair sequence has no stride-2 stack: never read)
-            if ((st = psfm_batch_fill_seq_opt(c, D[i], flows_f[i], masks, P, f2, c->occ2_own.as<uint8_t>(),
+            if ((st = psfm_batch_fill_seq_opt(c, D[i], flows_f[i], masks, fP(i), f2, c->occ2_own.as<uint8_t>(),
                                               htabo + row_opt * (size_t)i, s)) != PSFM_OK) return st;
             // a run whose launches covered too few lanes has left the fused solve's tickets mid-count (blocks they were waiting
             // for never existed): the run that repeats it starts them from zero
@@ -512,7 +587,8 @@ psfm_status BatchRun::redo_alone(const std::vector<int>& redo, psfm_track_info* 
     const int room = own->resident_budget > 0 ? std::min(own->resident_budget, psfm_resident_blocks(own)) : psfm_resident_blocks(own);
     if (redo.size() >= 2 && optimize) {
         const int capacity = room;
-        const int64_t G = (int64_t)((w + ratio - 1) / ratio) * ((h + ratio - 1) / ratio);
+        int64_t G = 0;                                            // (the largest grid among them)
+        for (int i : redo) G = std::max(G, D[i].G);
         const int64_t need = (G * 6 / 10 + 767) / 768;            // blocks that hold ~60 % of the grid's tracks at three per thread
         int fit = need > 0 ? (int)(capacity / need) : 4;
         if (const char* e = getenv("PSFM_BATCH_REDO_THREADS")) fit = atoi(e);
@@ -522,7 +598,7 @@ psfm_status BatchRun::redo_alone(const std::vector<int>& redo, psfm_track_info* 
     }
     if (n_thr == 1) {
         for (int i : redo) {
-            st = psfm_connect(ctxs[i], flows_f[i], flows_b[i], optimize ? flows_f2[i] : nullptr, optimize ? flows_b2[i] : nullptr, n_flows[i], h, w, thres,
+            st = psfm_connect(ctxs[i], flows_f[i], flows_b[i], optimize ? flows_f2[i] : nullptr, optimize ? flows_b2[i] : nullptr, n_flows[i], fh(i), fw(i), thres,
                               ratio, nullptr, nullptr, infos ? &infos[i] : nullptr, stream);
             if (st != PSFM_OK) return st;
         }
@@ -542,7 +618,7 @@ psfm_status BatchRun::redo_alone(const std::vector<int>& redo, psfm_track_info* 
                 }
                 const int budget0 = c->resident_budget;
                 c->resident_budget = share;
-                const psfm_status r = psfm_connect(c, flows_f[i], flows_b[i], flows_f2[i], flows_b2[i], n_flows[i], h, w, thres, ratio, nullptr, nullptr,
+                const psfm_status r = psfm_connect(c, flows_f[i], flows_b[i], flows_f2[i], flows_b2[i], n_flows[i], fh(i), fw(i), thres, ratio, nullptr, nullptr,
                                                    infos ? &infos[i] : nullptr, (void*)c->redo_stream);
                 c->resident_budget = budget0;
                 if (r != PSFM_OK) { rc[(size_t)t] = r; msg[(size_t)t] = psfm_last_error(); return; }      // (the error text is thread local)
@@ -591,9 +667,9 @@ psfm_status BatchRun::redo_together(const std::vector<int>& redo, psfm_track_inf
         psfm_call_begin(c, n_flows[i], false);       // (a sequence that left at a checkpoint has solves on file: from the top)
         S[i].total_iters = 0;
         const uint8_t* masks = mb ? c->kill.as<uint8_t>() : c->occ_own.as<uint8_t>();
-        psfm_batch_fill_seq(c, D[i], flows_f[i], masks, P, &htab[q]);      // (owner_clear: the stamp-wrap clear of the blocked map, on the device)
+        psfm_batch_fill_seq(c, D[i], flows_f[i], masks, fP(i), &htab[q]);      // (owner_clear: the stamp-wrap clear of the blocked map, on the device)
         const float* f2 = n_flows[i] > 1 ? flows_f2[i] : flows_f[i];
-        if ((st = psfm_batch_fill_seq_opt(c, D[i], flows_f[i], masks, P, f2, c->occ2_own.as<uint8_t>(), hopt + row_opt * (size_t)q, s)) != PSFM_OK) return st;
+        if ((st = psfm_batch_fill_seq_opt(c, D[i], flows_f[i], masks, fP(i), f2, c->occ2_own.as<uint8_t>(), hopt + row_opt * (size_t)q, s)) != PSFM_OK) return st;
         if ((st = psfm_frame_row_fill(c, D[i], hopt + row_opt * (size_t)q, hfr + row_fr * (size_t)q, &nb[q])) != PSFM_OK) return st;
         if (n_flows[i] > n_top) n_top = n_flows[i];
         if (D[i].cap > cap_top) cap_top = D[i].cap;
@@ -655,12 +731,13 @@ psfm_status BatchRun::redo_together(const std::vector<int>& redo, psfm_track_inf
 
 static psfm_status batch_run(psfm_ctx* const* ctxs, int n_seq, const float* const* flows_f, const float* const* flows_b,
                              const float* const* flows_f2, const float* const* flows_b2, const int* n_flows, int h, int w,
-                             float thres, int ratio, psfm_track_info* infos, void* stream, bool trim, bool* grid_too_small)
+                             const int* hs, const int* ws, float thres, int ratio, psfm_track_info* infos, void* stream, bool trim,
+                             bool* grid_too_small)
 {
     *grid_too_small = false;
     // (the flow_check pipeline's events go back into the owner's pool when the call ends, however it ends)
-    BatchRun R{ctxs, n_seq, flows_f, flows_b, flows_f2, flows_b2, n_flows, h, w, thres, ratio, (hipStream_t)stream, trim, grid_too_small,
-               ctxs[0], flows_f2 != nullptr, ctxs[0]->mb_enable, (int64_t)h * w, PsfmOccPipeline(ctxs[0])};
+    BatchRun R{ctxs, n_seq, flows_f, flows_b, flows_f2, flows_b2, n_flows, h, w, hs, ws, thres, ratio, (hipStream_t)stream, trim, grid_too_small,
+               ctxs[0], flows_f2 != nullptr, ctxs[0]->mb_enable, PsfmOccPipeline(ctxs[0])};
     PSFM_HIP(hipSetDevice(R.own->device));
     // how the sequences that leave the fused batch are redone: the owner's psfm_ctx_set_batch_redo; PSFM_BATCH_REDO=together|alone
     // overrides it (measurements; read per call)

@@ -668,7 +668,7 @@ psfm_status psfm_finalize_persist(psfm_ctx* c, const PsfmTrackDims& d, bool* fal
 }
 
 // ------------------------------------------------------------------------------------------------
-// Segmented finalize of a BATCH (psfm_connect_batch): what psfm_finalize does for one sequence, for B same-shape sequences with ONE
+// Segmented finalize of a BATCH (psfm_connect_batch): what psfm_finalize does for one sequence, for B sequences (one key format) with ONE
 // host synchronisation, ONE radix sort and ONE scan.  A frame of a small sequence leaves a few ten thousand records: per
 // sequence the finalize is a dozen launch-latency-bound kernels and a host round trip -- as much time as its whole frame loop
 // takes inside a batch.  Here the records of all sequences go into one array under the key (sequence : key), are sorted once, and

@@ -222,7 +222,9 @@ struct psfm_ctx {
     size_t host_batch_bytes = 0;
     void* host_batch2 = nullptr;
     size_t host_batch2_bytes = 0;
-    int64_t batch_notrim_shape = 0;      // (h, w, sample_ratio, mode) whose sequences once outgrew launches trimmed to the lanes in use
+    int64_t batch_notrim_shape = 0;      // (h, w, sample_ratio, mode; the largest frame of a batch of several sizes) whose sequences once outgrew launches trimmed to the lanes in use
+    int batch_h = 0, batch_w = 0;        // psfm_ctx_set_frame_size: the frame size of the sequence this context holds in a psfm_connect_batch
+                                         // call with h = w = 0 (sequences of different frame sizes); 0, 0: none.  Nothing else reads it
     int batch_redo = 0;                  // psfm_ctx_set_batch_redo (read from the batch's owner): sequences that leave the fused batch run
                                          // 0 alone through psfm_connect, 1 together through the frame-mode multi-problem launch chain
     // the census of the last psfm_connect_batch (psfm_connect_batch_census): sequences that left the fused batch, those that went through
@@ -438,7 +440,7 @@ psfm_status psfm_qb_run(psfm_ctx* const* ctxs, int n_seq, const float* const* fl
                         const double* const* q_xy, const int32_t* const* q_t, const int64_t* n_q, psfm_track_info* infos_host, void* stream,
                         const PsfmQbHooks* hooks);
 
-// ---- batch: B same-shape sequences per launch (psfm_batch.hip; kernels beside their single-sequence forms) --------------------
+// ---- batch: B sequences per launch (psfm_batch.hip; kernels beside their single-sequence forms) -------------------------------
 #define PSFM_BATCH_MAX 64
 struct PsfmBatchSeq;      // psfm_chain_step.h: one row of the batch table (chain-step arguments of frame 1 + strides)
 struct PsfmFcSeq { const float* ff; const float* fb; uint8_t* occ; int n_pairs; int pad; };      // one stack of a batch for flow_check
@@ -456,6 +458,17 @@ psfm_status psfm_launch_chain_step_batch_mb(psfm_ctx* owner, const PsfmBatchSeq*
 struct PsfmKmSeq { const float* flows; const uint8_t* occ; uint8_t* out; int n; float thres; };
 bool psfm_kill_map_batch_vec_ok(int h, int w, const void* flows);
 psfm_status psfm_launch_kill_map_batch(const PsfmKmSeq* tab_dev, int n_seq, int pair0, int n_pairs, int h, int w, bool vec, hipStream_t s);
+// ... of stacks of DIFFERENT frame sizes (psfm_connect_batch with h = w = 0; rows, flattened grid and block rule: psfm_batch_shapes.h).
+// psfm_*_shape_row fills a row from the stack and its frame size, all but its place in the grid (psfm_bs_fc_prefix / psfm_bs_km_prefix,
+// which give `blocks`); the launches cover frames [pair0, pair0 + n_pairs) of every stack, as the two above.  Every stack has passed
+// psfm_flow_check_batch_ok for its own frame size.
+struct PsfmFcShapeRow;
+struct PsfmKmShapeRow;
+void psfm_fc_shape_row(const PsfmFcSeq& q, int h, int w, PsfmFcShapeRow* row);
+psfm_status psfm_launch_flow_check_shapes(const PsfmFcShapeRow* tab_dev, const int* blk_end_dev, int blocks, int pair0, int n_pairs, float thres,
+                                          hipStream_t s);
+void psfm_km_shape_row(const PsfmKmSeq& q, int h, int w, PsfmKmShapeRow* row);
+psfm_status psfm_launch_kill_map_shapes(const PsfmKmShapeRow* tab_dev, const int* blk_end_dev, int blocks, int pair0, int n_pairs, hipStream_t s);
 // track_optimize rows (psfm_solver_batch.hip: chain-step arguments + solver parameters of frame 1 + strides) and their launches
 size_t psfm_batch_seq_opt_bytes(void);
 psfm_status psfm_batch_fill_seq_opt(psfm_ctx* c, const PsfmTrackDims& d, const float* flows, const uint8_t* occ, int64_t occ_pitch,

@@ -12,6 +12,7 @@
 #include "psfm_internal.h"
 #include "psfm_motion_boundary.h"
 #include "psfm_chain_step.h"
+#include "psfm_batch_shapes.h"
 
 #define PSFM_MB_BLOCK 256
 #define PSFM_MB_PPL 4             // pixels per lane: 32 bytes of flow = two 16-byte loads, 4 result bytes = one 32-bit store
@@ -326,6 +327,55 @@ __global__ __launch_bounds__(PSFM_MB_BLOCK) void psfm_kill_map_batch_px_kernel(c
     t.out[base + p] = (uint8_t)((t.occ[base + p] != 0 ? PSFM_KILL_OCC : 0u) | (v ? PSFM_KILL_MB : 0u));
 }
 
+// ... and for stacks of DIFFERENT frame sizes (psfm_connect_batch with h = w = 0): blockIdx.x runs over the blocks of all stacks
+// (psfm_batch_shapes.h), blockIdx.y = frame pair0 + y.  The frame, the band rule and the form are the row's -- four pixels per lane
+// with W even or odd, or one pixel per thread -- and the switch between them is block-uniform; inside a form the block does what the
+// block of the launch above does for the same chunk of the same frame (the same fast / guarded decision from the row's P, W and n).
+static_assert(PSFM_BS_KM_LANES == PSFM_MB_BLOCK && PSFM_BS_KM_PPL == PSFM_MB_PPL, "psfm_batch_shapes.h counts the chunks of these kernels");
+template <bool WEVEN>
+__device__ __forceinline__ void psfm_km_shapes_lanes(const PsfmKmShapeRow& t, const PsfmKmArgs& a, int chunk, int f)
+{
+    const int64_t F0 = (int64_t)f * a.P;
+    const float2* F = (const float2*)t.flows + F0;
+    const uint8_t* occ = t.occ + F0;
+    uint8_t* out = t.out + F0;
+    const int r_blk = chunk * (PSFM_MB_BLOCK * PSFM_MB_PPL);
+    const int r0 = r_blk + (int)threadIdx.x * PSFM_MB_PPL;
+    const int r_last = r_blk + (PSFM_MB_BLOCK - 1) * PSFM_MB_PPL;
+    const bool al4 = ((((uintptr_t)occ) | ((uintptr_t)out)) & 3) == 0;
+    const bool fast = al4 & (r_last + PSFM_MB_PPL <= a.P) & (F0 + r_last + a.W + PSFM_MB_PPL <= (int64_t)t.n * a.P);
+    if (fast) {
+        psfm_km_lane<WEVEN, true>(F, occ, out, a, r0, t.thres, true);
+    } else {
+        if (r0 >= a.P) return;
+        psfm_km_lane<WEVEN, false>(F, occ, out, a, r0, t.thres, al4);
+    }
+}
+
+__global__ __launch_bounds__(PSFM_MB_BLOCK) void psfm_kill_map_shapes_kernel(const PsfmKmShapeRow* __restrict__ T, const int* __restrict__ blk_end,
+                                                                          int pair0)
+{
+    const int b = __builtin_amdgcn_readfirstlane(psfm_bs_find(blk_end, (int)blockIdx.x));
+    const PsfmKmShapeRow& t = T[b];
+    const int f = pair0 + (int)blockIdx.y;
+    if (f >= t.n) return;                                                  // a stack is touched only where it has frames
+    const int chunk = psfm_bs_chunk((int)blockIdx.x - t.blk0, t.chunks, t.xcd_per);
+    if (chunk < 0) return;                                                 // (a spare block: the stack's count is rounded up to 8)
+    PsfmKmArgs a;
+    a.H = t.H; a.W = t.W; a.P = t.P; a.pair0 = pair0; a.chunks = t.chunks; a.xcd_per = t.xcd_per; a.wdiv = t.wdiv;
+    const int form = t.form;
+    if (form == PSFM_BS_KM_LANE_WEVEN) psfm_km_shapes_lanes<true>(t, a, chunk, f);
+    else if (form == PSFM_BS_KM_LANE_WODD) psfm_km_shapes_lanes<false>(t, a, chunk, f);
+    else {
+        const int p = chunk * PSFM_MB_BLOCK + (int)threadIdx.x;
+        if (p >= a.P) return;
+        const int64_t base = (int64_t)f * a.P;
+        const int y = (int)psfm_fastdiv((unsigned)p, a.wdiv), x = p - y * a.W;
+        const unsigned v = psfm_mb_at((const float2*)t.flows + base, x, y, a.H, a.W, t.thres);
+        t.out[base + p] = (uint8_t)((t.occ[base + p] != 0 ? PSFM_KILL_OCC : 0u) | (v ? PSFM_KILL_MB : 0u));
+    }
+}
+
 // the table of a psfm_kill_map_batch call travels in this kernel's arguments (read when the launch is enqueued: the caller's arrays may
 // go away as soon as the call returns) and is stored where the launch behind it finds it
 struct PsfmKmTab { PsfmKmSeq row[PSFM_BATCH_MAX]; };
@@ -352,6 +402,29 @@ psfm_status psfm_launch_kill_map_batch(const PsfmKmSeq* tab_dev, int n_seq, int 
         if (!vec) hipLaunchKernelGGL(psfm_kill_map_batch_px_kernel, grid, block, 0, s, tab_dev, a);
         else if ((w & 1) == 0) hipLaunchKernelGGL(psfm_kill_map_batch_kernel<true>, grid, block, 0, s, tab_dev, a);
         else hipLaunchKernelGGL(psfm_kill_map_batch_kernel<false>, grid, block, 0, s, tab_dev, a);
+    }
+    PSFM_HIP(hipGetLastError());
+    return PSFM_OK;
+}
+
+// stacks of different frame sizes: a stack's row (its place in the flattened grid apart: psfm_bs_km_prefix) and the launch
+void psfm_km_shape_row(const PsfmKmSeq& q, int h, int w, PsfmKmShapeRow* row)
+{
+    memset(row, 0, sizeof(*row));
+    row->flows = q.flows; row->occ = q.occ; row->out = q.out; row->n = q.n; row->thres = q.thres;
+    row->H = h; row->W = w; row->P = h * w;
+    row->wdiv = psfm_fastdiv_make((unsigned)w);
+    row->form = psfm_bs_km_form(row->P, w, ((uintptr_t)q.flows % 16) == 0);
+    row->chunks = psfm_bs_km_chunks(row->P, row->form);
+    row->xcd_per = row->form == PSFM_BS_KM_PX ? 0 : psfm_bs_xcd_per(row->chunks);
+}
+
+psfm_status psfm_launch_kill_map_shapes(const PsfmKmShapeRow* tab_dev, const int* blk_end_dev, int blocks, int pair0, int n_pairs, hipStream_t s)
+{
+    if (n_pairs <= 0 || blocks <= 0) return PSFM_OK;
+    for (int f0 = 0; f0 < n_pairs; f0 += 32768) {            // (gridDim.y < 65536)
+        const dim3 grid((unsigned)blocks, (unsigned)(n_pairs - f0 < 32768 ? n_pairs - f0 : 32768)), block(PSFM_MB_BLOCK);
+        hipLaunchKernelGGL(psfm_kill_map_shapes_kernel, grid, block, 0, s, tab_dev, blk_end_dev, pair0 + f0);
     }
     PSFM_HIP(hipGetLastError());
     return PSFM_OK;

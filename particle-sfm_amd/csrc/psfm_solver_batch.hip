@@ -8,7 +8,7 @@
 #include "psfm_solver_internal.h"
 
 // ------------------------------------------------------------------------------------------------
-// B same-shape sequences per launch (psfm_connect_batch; run_particlesfm.py:168-176 walks a directory of sequences): a frame of a
+// B sequences per launch, of one frame size or each of its own -- a row holds its sequence's -- (psfm_connect_batch; run_particlesfm.py:168-176 walks a directory of sequences): a frame of a
 // DAVIS / Sintel / ScanNet-sized sequence is a few hundred blocks -- 10-40 % of the device's block slots -- for one dependent chain
 // of round trips.  blockIdx.y = sequence: every sequence keeps its own context (lanes, log, counters, tickets, control block), its
 // own device-side program counter and K, so the sequences advance independently -- one may be continuing a solve while its

@@ -23,6 +23,7 @@
 
 #include "psfm_internal.h"
 #include "psfm_chain.h"
+#include "psfm_batch_shapes.h"
 
 #define PSFM_BLOCK 256
 
@@ -184,6 +185,49 @@ __device__ __forceinline__ void psfm_flow_check_x2v_body(const float2* __restric
     }
 }
 
+// The same body for a block that is NOT block blockIdx.x of its frame pair: `block` is its number inside its sequence where the grid is
+// flattened over sequences of different frame sizes (psfm_flow_check_x2v_shapes_kernel).  A copy, statement for statement, so that the
+// kernels above keep the instructions they had.
+template <bool NT>
+__device__ __forceinline__ void psfm_flow_check_x2v_body_at(const float2* __restrict__ F, const float2* __restrict__ B, const PsfmFcParams& q,
+                                                            uint8_t* __restrict__ occ_pair, const PsfmFastDiv& wdiv, int xcd_per, int block)
+{
+    const int P = q.H * q.W;                      // (even: the launcher falls back to the x4 kernel otherwise)
+    const int bx = psfm_xcd_chunk(block, xcd_per);
+    if ((int64_t)bx * (PSFM_BLOCK * PSFM_FC2_UNROLL * 2) >= P) return;
+    const int p0 = (bx * (PSFM_BLOCK * PSFM_FC2_UNROLL) + threadIdx.x) * 2;
+    float4 f[PSFM_FC2_UNROLL];
+#pragma unroll
+    for (int k = 0; k < PSFM_FC2_UNROLL; ++k) {
+        const int p = p0 + k * PSFM_BLOCK * 2;
+        typedef float psfm_v4f __attribute__((ext_vector_type(4)));
+        const float4* src = (const float4*)((const char*)F + (unsigned)p * 8u);
+        if (p >= P) f[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+        else if (NT) { const psfm_v4f v = __builtin_nontemporal_load((const psfm_v4f*)src); f[k] = make_float4(v.x, v.y, v.z, v.w); }
+        else f[k] = *src;
+    }
+#pragma unroll
+    for (int k = 0; k < PSFM_FC2_UNROLL; ++k) {
+        const int p = p0 + k * PSFM_BLOCK * 2;
+        if (p >= P) break;
+        const int y = (int)psfm_fastdiv((unsigned)p, wdiv), x = p - y * q.W;
+        int x1 = x + 1, y1 = y;
+        if (x1 >= q.W) { x1 = 0; ++y1; }
+        uchar2 o;
+        const float2 fa = make_float2(f[k].x, f[k].y), fb = make_float2(f[k].z, f[k].w);
+        const PsfmFcGeom ga = psfm_fc_geom(x, y, fa, q), gb = psfm_fc_geom(x1, y1, fb, q);
+        if (__builtin_amdgcn_ballot_w64(!(ga.interior & gb.interior)) == 0ull) {
+            o.x = psfm_flow_check_px16<true>(B, fa, ga, q);
+            o.y = psfm_flow_check_px16<true>(B, fb, gb, q);
+        } else {
+            o.x = psfm_flow_check_px16<false>(B, fa, ga, q);
+            o.y = psfm_flow_check_px16<false>(B, fb, gb, q);
+        }
+        if (NT) __builtin_nontemporal_store(*(unsigned short*)&o, (unsigned short*)(occ_pair + p));
+        else *(uchar2*)(occ_pair + p) = o;
+    }
+}
+
 template <bool NT>
 __global__ __launch_bounds__(PSFM_BLOCK) void psfm_flow_check_x2v_kernel(
     const float2* __restrict__ flows_f, const float2* __restrict__ flows_b, PsfmFcParams q, uint8_t* __restrict__ occ_out, PsfmFastDiv wdiv,
@@ -202,6 +246,27 @@ __global__ __launch_bounds__(PSFM_BLOCK) void psfm_flow_check_x2v_batch_kernel(c
     if (pair >= t.n_pairs) return;
     const int64_t base = (int64_t)pair * (q.H * q.W);
     psfm_flow_check_x2v_body<false>((const float2*)t.ff + base, (const float2*)t.fb + base, q, t.occ + base, wdiv, xcd_per);
+}
+
+// ... and for stacks of DIFFERENT frame sizes (psfm_connect_batch with h = w = 0): blockIdx.x runs over the blocks of all sequences
+// (psfm_batch_shapes.h: the block finds its sequence in the inclusive prefix and is block `local` of that sequence's frame pair),
+// blockIdx.y = frame pair pair0 + y.  Everything the body reads comes from the sequence's row, through scalar loads -- the row's
+// address is block-uniform -- so the per-pixel arithmetic is the uniform kernel's and so are the maps.
+static_assert(PSFM_BS_FC_PIXELS == PSFM_BLOCK * PSFM_FC2_UNROLL * 2, "psfm_batch_shapes.h counts the chunks of the x2v body");
+__global__ __launch_bounds__(PSFM_BLOCK) void psfm_flow_check_x2v_shapes_kernel(const PsfmFcShapeRow* __restrict__ T,
+                                                                                const int* __restrict__ blk_end, float thres, float t2, int pair0)
+{
+    const int b = __builtin_amdgcn_readfirstlane(psfm_bs_find(blk_end, (int)blockIdx.x));
+    const PsfmFcShapeRow& t = T[b];
+    const int pair = pair0 + (int)blockIdx.y;
+    if (pair >= t.n_pairs) return;
+    const int local = (int)blockIdx.x - t.blk0;
+    if (psfm_bs_chunk(local, t.chunks, t.xcd_per) < 0) return;      // (a spare block: the sequence's count is rounded up to 8)
+    PsfmFcParams q;
+    q.H = t.H; q.W = t.W; q.cw = t.cw; q.ch = t.ch; q.rcw = t.rcw; q.rch = t.rch; q.thres = thres; q.t2 = t2;
+    const PsfmFastDiv wdiv = t.wdiv;
+    const int64_t base = (int64_t)pair * (q.H * q.W);
+    psfm_flow_check_x2v_body_at<false>((const float2*)t.ff + base, (const float2*)t.fb + base, q, t.occ + base, wdiv, t.xcd_per, local);
 }
 
 PsfmFcParams psfm_fc_params(int h, int w, float thres);
@@ -345,6 +410,29 @@ psfm_status psfm_launch_flow_check_batch(const PsfmFcSeq* tab_dev, int n_seq, in
     return PSFM_OK;
 }
 
+// stacks of different frame sizes: a stack's row (its place in the flattened grid apart: psfm_bs_fc_prefix) and the launch
+void psfm_fc_shape_row(const PsfmFcSeq& s, int h, int w, PsfmFcShapeRow* row)
+{
+    const PsfmFcParams q = psfm_fc_params(h, w, 0.0f);
+    memset(row, 0, sizeof(*row));
+    row->ff = s.ff; row->fb = s.fb; row->occ = s.occ; row->n_pairs = s.n_pairs;
+    row->H = h; row->W = w; row->cw = q.cw; row->ch = q.ch; row->rcw = q.rcw; row->rch = q.rch;
+    row->wdiv = psfm_fastdiv_make((unsigned)w);
+    row->chunks = psfm_bs_fc_chunks((int64_t)h * w);
+    row->xcd_per = psfm_xcd_per(row->chunks);
+}
+
+psfm_status psfm_launch_flow_check_shapes(const PsfmFcShapeRow* tab_dev, const int* blk_end_dev, int blocks, int pair0, int n_pairs, float thres,
+                                          hipStream_t s)
+{
+    if (n_pairs <= 0 || blocks <= 0) return PSFM_OK;
+    const PsfmFcParams q = psfm_fc_params(2, 2, thres);      // (the threshold and its square: the frame's constants are the rows')
+    hipLaunchKernelGGL(psfm_flow_check_x2v_shapes_kernel, dim3((unsigned)blocks, (unsigned)n_pairs), dim3(PSFM_BLOCK), 0, s, tab_dev, blk_end_dev,
+                       q.thres, q.t2, pair0);
+    PSFM_HIP(hipGetLastError());
+    return PSFM_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // trajectory.py:25-37 exposed as an API (parity tests, optimize_buffer-style callers)
 // ------------------------------------------------------------------------------------------------
@@ -448,7 +536,7 @@ __global__ __launch_bounds__(PSFM_CHAIN_BLOCK) PSFM_CHAIN_WAVES void psfm_chain_
     (void)psfm_chain_step_body<R, OPT, false>(a, o);
 }
 
-// ---- batched forms (psfm_batch.hip): B same-shape sequences, blockIdx.y = sequence, gridDim.x a multiple of 8 (workgroups go to
+// ---- batched forms (psfm_batch.hip): B sequences (every dimension from the sequence's row), blockIdx.y = sequence, gridDim.x a multiple of 8 (workgroups go to
 // the XCDs round-robin by linear id: block (x, y) then still sits on XCD x % 8, which psfm_xcd_tile counts on) ----
 template <int R, bool OPT>
 __global__ __launch_bounds__(PSFM_CHAIN_BLOCK) PSFM_CHAIN_WAVES void psfm_chain_step_batch_kernel(const PsfmBatchSeq* __restrict__ seqs, int frame)

@@ -41,7 +41,7 @@ EXPORTS = [
     "psfm_result_filter_batch", "psfm_traj_to_matches_batch", "psfm_labels_to_matches_batch", "psfm_matches_batch_census", "psfm_labels_sizes",
     "psfm_track_queries_batch", "psfm_query_batch_census",
     "psfm_track_queries_optimize_batch", "psfm_query_pc_batch_census",
-    "psfm_ctx_set_batch_redo", "psfm_connect_batch_census",
+    "psfm_ctx_set_batch_redo", "psfm_connect_batch_census", "psfm_ctx_set_frame_size",
 ]
 
 
@@ -107,6 +107,7 @@ def lib():
     L.psfm_connect_batch.argtypes = [ctypes.POINTER(vp), i32, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp),
                                      ctypes.POINTER(i32), i32, i32, f32, i32, ctypes.POINTER(TrackInfo), vp]
     L.psfm_ctx_set_batch_redo.argtypes = [vp, i32]
+    L.psfm_ctx_set_frame_size.argtypes = [vp, i32, i32]
     L.psfm_connect_batch_census.argtypes = [vp] + [ctypes.POINTER(ctypes.c_int32)] * 5
     L.psfm_track_queries.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, i64, ctypes.POINTER(TrackInfo), vp]
     L.psfm_track_queries_optimize.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, i64, ctypes.POINTER(TrackInfo), vp]
@@ -264,6 +265,11 @@ class Context:
         mode = self.BATCH_REDO.get(mode, mode)
         check(lib().psfm_ctx_set_batch_redo(self._h, int(mode)))
         self.batch_redo = int(mode)
+
+    def set_frame_size(self, h, w):
+        """The frame size of the sequence this context holds in a psfm_connect_batch call with h = w = 0 (sequences of different frame
+        sizes in one batch); (0, 0) clears it.  No other entry point reads it."""
+        check(lib().psfm_ctx_set_frame_size(self._h, int(h), int(w)))
 
     def connect_batch_census(self):
         """The last psfm_connect_batch call that had this context as its first: sequences that left the fused batch, those that were

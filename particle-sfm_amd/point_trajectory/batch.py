@@ -25,9 +25,10 @@ BATCH_BYTES = 48 << 30         # flow stacks of one group resident in HBM before
 
 
 def _connect_batch_to_disk(flow_dirs, traj_dirs, sample_ratio, flow_check_thres, traj_min_len, skip_path_consistency, skip_exists, layout,
-                           motion_boundary=False, mb_thres=0.02, mb_engine=None, redo=None):
+                           motion_boundary=False, mb_thres=0.02, mb_engine=None, redo=None, mixed=False):
     """main_connect_point_trajectories.py:27-62 for a group of sequences through psfm_connect_batch: ingest all, ONE batched
-    compute call per frame size, then filter + save each from its own context.  motion_boundary / mb_thres / mb_engine / redo: as in run_connect_batch
+    compute call per frame size (mixed=True: one for all frame sizes together), then filter + save each from its own context.
+    motion_boundary / mb_thres / mb_engine / redo: as in run_connect_batch
     (the PSFM_MOTION_BOUNDARY switch of the one-sequence entry point holds here too)."""
     import os
     from .utils import load_flows_device
@@ -44,7 +45,8 @@ def _connect_batch_to_disk(flow_dirs, traj_dirs, sample_ratio, flow_check_thres,
             ts = result_to_trajectory_set(ctx, info, traj_min_len, reuse_pinned=True)
             save_track_npy(os.path.join(td, "track.npy"), ts, layout=layout)
 
-    # Groups of one frame size go through psfm_connect_batch as they fill up: at most PSFM_BATCH_MAX (64) sequences and BATCH_BYTES of
+    # Groups of one frame size (mixed: ONE group, whatever the frame sizes -- psfm_connect_batch takes them together) go through
+    # psfm_connect_batch as they fill up: at most PSFM_BATCH_MAX (64) sequences and BATCH_BYTES of
     # flow stacks in HBM at a time (a group is ingested whole before its compute starts).  A directory without flows, or one whose
     # frames cannot be read here, goes through the one-sequence entry point, which reports / handles it by itself -- it must not take
     # the other sequences of the call with it.
@@ -62,7 +64,7 @@ def _connect_batch_to_disk(flow_dirs, traj_dirs, sample_ratio, flow_check_thres,
         f2 = b2 = None
         if not skip_path_consistency:
             f2, b2 = load_flows_device(os.path.join(fd, "flow_f2")), load_flows_device(os.path.join(fd, "flow_b2"))
-        key = (int(f.shape[1]), int(f.shape[2]))
+        key = None if mixed else (int(f.shape[1]), int(f.shape[2]))
         by_shape.setdefault(key, []).append((td, (f, b, f2, b2)))
         held[key] = held.get(key, 0) + sum(int(t.numel()) * 4 for t in (f, b, f2, b2) if t is not None)
         if len(by_shape[key]) >= BATCH_MAX or held[key] >= BATCH_BYTES:
@@ -75,8 +77,13 @@ def _connect_batch_to_disk(flow_dirs, traj_dirs, sample_ratio, flow_check_thres,
 
 def connect_sequences(flow_dirs, traj_dirs, sample_ratio=2, flow_check_thres=1.0, traj_min_len=3,
                       skip_path_consistency=False, skip_exists=False, concurrency=2, rank=None, world=None, layout="csr", batch=1,
-                      motion_boundary=False, mb_thres=0.02, mb_engine=None, redo=None):
+                      motion_boundary=False, mb_thres=0.02, mb_engine=None, redo=None, mixed=False):
     """main_connect_point_trajectories for a list of sequences; returns the indices this rank processed.
+    mixed (batch > 1): False -- the sequences a worker takes are grouped by frame size, one psfm_connect_batch call per size; True -- they
+    go through ONE call whatever their sizes (a directory of videos of several resolutions keeps full batches).  Same files.  Off by
+    default: measured on an MI355X, one call is 1.27-1.7x faster than one per size where the size groups are small (16 sequences of
+    four sizes); where every group fills the device by itself (64 of four sizes) it is 1.08x faster in track mode, level with path
+    consistency and 1.24x slower with the motion boundary (profiles/EXPERIMENTS.md section 34).
     redo (batch > 1, path consistency): how sequences that leave a batch are run again -- "alone", "together" or None (as
     run_connect_batch: the contexts' setting, "alone" by default).
     layout: pickle state of the track.npy files -- "csr" (default here: the batch driver is this package's own entry
@@ -127,7 +134,7 @@ def connect_sequences(flow_dirs, traj_dirs, sample_ratio=2, flow_check_thres=1.0
                     if batch > 1:
                         _connect_batch_to_disk([flow_dirs[k] for k in ks], [traj_dirs[k] for k in ks], sample_ratio, flow_check_thres,
                                                traj_min_len, skip_path_consistency, skip_exists, layout, motion_boundary=motion_boundary,
-                                               mb_thres=mb_thres, mb_engine=mb_engine, redo=redo)
+                                               mb_thres=mb_thres, mb_engine=mb_engine, redo=redo, mixed=mixed)
                         continue
                     main_connect_point_trajectories(flow_dirs[k], traj_dirs[k], sample_ratio=sample_ratio,
                                                     flow_check_thres=flow_check_thres, traj_min_len=traj_min_len,

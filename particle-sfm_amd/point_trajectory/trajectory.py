@@ -368,10 +368,11 @@ MB_ENGINE_DEFAULT = "batch"
 
 
 def run_connect_batch(seqs, thres, sample_ratio, motion_boundary=False, mb_thres=0.02, mb_engine=None, redo=None):
-    """psfm_connect_batch: flow_check + track / track_optimize for a BATCH of same-shape sequences (the directory of sequences the
+    """psfm_connect_batch: flow_check + track / track_optimize for a BATCH of sequences (the directory of sequences the
     reference's driver walks, run_particlesfm.py:168-176) with every frame launch covering the whole batch.
-    seqs: list of (flows_f, flows_b, flows_f2 | None, flows_b2 | None) device tensors (n_i,H,W,2) -- all with stride-2 stacks or
-    none.  Returns (contexts, infos): context i holds sequence i's result (`_result_to_host(ctx, info)`,
+    seqs: list of (flows_f, flows_b, flows_f2 | None, flows_b2 | None) device tensors (n_i,H_i,W_i,2) -- all with stride-2 stacks or
+    none.  Sequences of one frame size make the call with that size; with several sizes every batch context is given its sequence's
+    (Context.set_frame_size, cleared again behind the call) and the call is made with h = w = 0: same results.  Returns (contexts, infos): context i holds sequence i's result (`_result_to_host(ctx, info)`,
     `result_to_trajectory_set(ctx, info)`) until the calling thread's next batch.
     motion_boundary: tracks also die on motion boundaries of threshold mb_thres (one value, or one per sequence).  mb_engine "batch":
     the option is set on every batch context for the duration of the call and the batched launches form the verdict; "loop": the
@@ -399,15 +400,19 @@ def run_connect_batch(seqs, thres, sample_ratio, motion_boundary=False, mb_thres
             infos = [run_connect(a, b, a2, b2_, thres, sample_ratio, return_device=True, motion_boundary=True, mb_thres=t, ctx=c)
                      for c, t, (a, b, a2, b2_) in zip(ctxs, mb_list, seqs)]
             return ctxs, infos
-    H, W = int(seqs[0][0].shape[1]), int(seqs[0][0].shape[2])
+    shapes = [(int(a.shape[1]), int(a.shape[2])) for a, _, _, _ in seqs]
+    H, W = shapes[0]
+    mixed = any(sh != shapes[0] for sh in shapes)      # several frame sizes: every batch context carries its sequence's, the call has h = w = 0
     opt = seqs[0][2] is not None
     keep = []           # (tensors created here must outlive the call)
     nf = (ctypes.c_int * n_seq)()
     vp = ctypes.c_void_p
     ff, fb, f2, b2 = (vp * n_seq)(), (vp * n_seq)(), (vp * n_seq)(), (vp * n_seq)()
     for i, (a, b, a2, b2_) in enumerate(seqs):
-        if int(a.shape[1]) != H or int(a.shape[2]) != W or (a2 is not None) != opt:
-            raise ValueError("connect_batch: sequence %d differs in frame size / stride-2 stacks from sequence 0" % i)
+        if (a2 is not None) != opt:
+            raise ValueError("connect_batch: sequence %d differs in stride-2 stacks from sequence 0 (all sequences with them, or none)" % i)
+        if tuple(b.shape[1:3]) != shapes[i] or (a2 is not None and a2.numel() > 0 and (tuple(a2.shape[1:3]) != shapes[i] or tuple(b2_.shape[1:3]) != shapes[i])):
+            raise ValueError("connect_batch: the stacks of sequence %d differ in frame size" % i)
         n = min(int(a.shape[0]), int(b.shape[0]))
         if n < 1:
             raise ValueError("connect_batch: sequence %d has no flow field" % i)
@@ -417,16 +422,20 @@ def run_connect_batch(seqs, thres, sample_ratio, motion_boundary=False, mb_thres
         ff[i], fb[i] = a.data_ptr(), b.data_ptr()
         if opt:
             if a2.numel() == 0:
-                a2 = b2_ = torch.zeros((1, H, W, 2), dtype=torch.float32, device=a.device)
+                a2 = b2_ = torch.zeros((1,) + shapes[i] + (2,), dtype=torch.float32, device=a.device)
                 keep.append(a2)
             f2[i], b2[i] = a2.data_ptr(), b2_.data_ptr()
     ctxs = _hip.batch_contexts(n_seq)
     handles = (vp * n_seq)(*[c.handle for c in ctxs])
     infos = (_hip.TrackInfo * n_seq)()
-    cap_key = ("batch", H, W, int(sample_ratio), opt)
+    cap_key = ("batch", tuple(sorted(set(shapes))), int(sample_ratio), opt) if mixed else ("batch", H, W, int(sample_ratio), opt)
     lane_f, traj_f = _capacity_of(ctxs[0], cap_key)
     redo_before = ctxs[0].batch_redo
     try:
+        if mixed:
+            for c, (hi, wi) in zip(ctxs, shapes):
+                c.set_frame_size(hi, wi)
+            H = W = 0
         if redo is not None:
             ctxs[0].set_batch_redo(redo)
         if mb_list is not None:
@@ -447,6 +456,9 @@ def run_connect_batch(seqs, thres, sample_ratio, motion_boundary=False, mb_thres
                 c.set_motion_boundary(False)
         if redo is not None:
             ctxs[0].set_batch_redo(redo_before)
+        if mixed:                    # (as the option: per context, and the thread's batch contexts are reused)
+            for c in ctxs:
+                c.set_frame_size(0, 0)
     _hip.check(st)
     return ctxs, [infos[i] for i in range(n_seq)]
 
