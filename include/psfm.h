@@ -261,6 +261,13 @@ psfm_status psfm_ctx_get_finalize_forms(psfm_ctx* ctx, int* sort_form, int* offs
  * sort_form above reports 1 either way; the bytes of the result are the same.  *placed: 0 / 1.  Reads host-side state only. */
 psfm_status psfm_ctx_get_finalize_placed(psfm_ctx* ctx, int* placed);
 
+/* How the LAST id assignment of this context turned the persistent loop's flow log into positions.  *gather: 0 no flow log (the
+ * per-frame kernels log positions), 1 one thread per trajectory adds the flows in the loop's order, 2 the lanes that store a
+ * trajectory's 32 positions sum them as a prefix sum, and redo in the loop's order the chunks in which an addition could round
+ * (csrc/psfm_gather_exact.h; frames up to 3840 pixels a side; PSFM_FIN_GATHER=0 in the environment keeps 1).  The bytes of the
+ * result are the same.  Reads host-side state only. */
+psfm_status psfm_ctx_get_finalize_gather(psfm_ctx* ctx, int* gather);
+
 /* track.py:24-50 when flows_f2 == NULL, track_optimize.py:24-53 otherwise.
  *   flows    (n_flows,H,W,2) f32      occ     (n_flows,H,W) u8
  *   flows_f2 (n_flows-1,H,W,2) f32    occ_s2  (n_flows-1,H,W) u8        (stride-2 stacks)

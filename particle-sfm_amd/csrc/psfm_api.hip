@@ -435,6 +435,13 @@ extern "C" psfm_status psfm_ctx_get_finalize_placed(psfm_ctx* c, int* placed)
     return PSFM_OK;
 }
 
+extern "C" psfm_status psfm_ctx_get_finalize_gather(psfm_ctx* c, int* gather)
+{
+    PSFM_CHECK_CTX(c);
+    if (gather) *gather = c->fin_gather;
+    return PSFM_OK;
+}
+
 // Sizes of one run of the frame recurrence.  g_own < 0: the whole stride-r grid; otherwise the number of grid points whose
 // births this process owns (track-sharded runs): lane / record tables are sized for those, keys for the whole grid.
 psfm_status psfm_track_dims(psfm_ctx* c, int n_flows, int h, int w, int ratio, int64_t g_own, PsfmTrackDims& d)

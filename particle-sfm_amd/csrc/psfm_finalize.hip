@@ -22,6 +22,7 @@
 
 #include "psfm_device.h"
 #include "psfm_finalize_plan.h"
+#include "psfm_gather_exact.h"
 #include "psfm_internal.h"
 #include "psfm_place.h"
 
@@ -316,7 +317,8 @@ __global__ __launch_bounds__(PSFM_BLOCK) void psfm_gather_kernel(const double2* 
 // The persistent loop logs the sampled flow of every survived step instead of positions (half the bytes, written once,
 // read once): a trajectory is its birth grid point plus the running f64 sum of its column -- the additions the loop
 // itself performed, p(t+1) = p(t) + (double)flow, re-run here in the same order (one thread walks one trajectory's
-// chunk serially through LDS; a parallel scan would round differently whenever an addition is inexact).
+// chunk serially through LDS; a parallel scan would round differently whenever an addition is inexact).  Runs behind
+// PSFM_FIN_GATHER=0 and for frames the chunk rule does not cover (psfm_gx_form); psfm_gather_delta2_kernel below is the default.
 __global__ __launch_bounds__(PSFM_BLOCK) void psfm_gather_delta_kernel(const float2* __restrict__ dlog, int64_t cap,
                                                                        const int* __restrict__ lanes,
                                                                        const int* __restrict__ birth,
@@ -402,6 +404,149 @@ __global__ __launch_bounds__(PSFM_BLOCK) void psfm_gather_delta_kernel(const flo
         for (int jj = tid / TILE_K; jj < TILE_J; jj += PSFM_BLOCK / TILE_K) {
             const int t = k0 + kk;
             if (t < s_len[jj]) out[s_off[jj] + t] = tile[jj][kk];
+        }
+        __syncthreads();
+    }
+}
+
+// ---- the same gather with the sums formed in the WRITE layout (psfm_gather_exact.h) --------------------------------------------
+// The 32 lanes that store times k0 .. k0 + 31 of a trajectory also sum its flows: an inclusive prefix sum over the half-wave in
+// registers, plus the chunk's base position.  That is the loop's result bit for bit whenever no addition rounds -- the chunk rule of
+// psfm_gather_exact.h, voted on by the half-wave -- and a chunk that fails the rule is redone in the loop's order by the same lanes,
+// its trajectory flagged for good.  No f64 tile, no wave that sums while three wait: 19.5 KB of LDS, eight blocks per CU.
+
+// v of the lane d below in the lane's row of 16 (0 where the row ends): d = 1, 2, 4, 8
+template <int D>
+__device__ __forceinline__ double psfm_gx_row_shr(double v)
+{
+    const long long b = __double_as_longlong(v);
+    const int lo = __builtin_amdgcn_update_dpp(0, (int)(unsigned)(b & 0xffffffffll), 0x110 + D, 0xf, 0xf, false);
+    const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), 0x110 + D, 0xf, 0xf, false);
+    return __longlong_as_double(((long long)hi << 32) | (long long)(unsigned)lo);
+}
+// in the rows 1 and 3 of a wave: v of lane 15 of the row below; in the rows 0 and 2: 0
+__device__ __forceinline__ double psfm_gx_row_bcast15(double v)
+{
+    const long long b = __double_as_longlong(v);
+    const int lo = __builtin_amdgcn_update_dpp(0, (int)(unsigned)(b & 0xffffffffll), 0x142, 0xa, 0xf, false);
+    const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), 0x142, 0xa, 0xf, false);
+    return __longlong_as_double(((long long)hi << 32) | (long long)(unsigned)lo);
+}
+// inclusive prefix sum over each half-wave (32 lanes), five steps; every lane of the wave takes part
+__device__ __forceinline__ double psfm_gx_scan32(double v)
+{
+    v = v + psfm_gx_row_shr<1>(v);
+    v = v + psfm_gx_row_shr<2>(v);
+    v = v + psfm_gx_row_shr<4>(v);
+    v = v + psfm_gx_row_shr<8>(v);
+    return v + psfm_gx_row_bcast15(v);
+}
+
+#ifdef PSFM_GX_COUNT       // (measurement builds: how many (trajectory, chunk) pairs there were, and how many took the loop's order)
+__device__ unsigned long long psfm_gx_counts[2];
+extern "C" int psfm_gx_read_counts(unsigned long long* out)
+{
+    return hipMemcpyFromSymbol(out, HIP_SYMBOL(psfm_gx_counts), sizeof(unsigned long long) * 2) == hipSuccess ? 0 : 1;
+}
+#endif
+
+__global__ __launch_bounds__(PSFM_BLOCK) void psfm_gather_delta2_kernel(const float2* __restrict__ dlog, int64_t cap,
+                                                                        const int* __restrict__ lanes,
+                                                                        const int* __restrict__ birth,
+                                                                        const int* __restrict__ len,
+                                                                        const int64_t* __restrict__ off, int64_t n,
+                                                                        const void* __restrict__ keys, int use32, int shift_b,
+                                                                        int GW, int ratio, double2* __restrict__ out, PsfmPlan pl)
+{
+    static_assert(TILE_K == PSFM_GX_CHUNK && PSFM_WAVE == 2 * TILE_K, "a half-wave sums one trajectory's chunk");
+    __shared__ float2 dtile[TILE_J][TILE_K + 1];
+    __shared__ double2 s_pos[TILE_J];          // the position a trajectory's next chunk starts from (read and written by its half-wave)
+    __shared__ int s_lane[TILE_J], s_birth[TILE_J], s_len[TILE_J], s_sticky[TILE_J];
+    __shared__ int64_t s_off[TILE_J];
+    __shared__ int s_maxlen;
+    const int tid = threadIdx.x;
+    const int64_t id0 = (int64_t)blockIdx.x * TILE_J;
+    int hb = 0, hl = 0;
+    if (tid == 0) s_maxlen = 0;
+    __syncthreads();
+    if (tid < TILE_J) {
+        const int64_t id = id0 + tid;
+        const bool ok = id < n;
+        int b = 0, l = 0, idx = -1;
+        const int my_lane = ok ? lanes[id] : 0;
+        if (ok) psfm_track_header(pl, birth, len, id, &b, &l, &idx);
+        hb = b; hl = l;
+        s_lane[tid] = my_lane;
+        s_birth[tid] = b;
+        s_len[tid] = l;
+        s_sticky[tid] = 0;
+        double2 p0 = make_double2(0.0, 0.0);
+        if (ok) {
+            atomicMax(&s_maxlen, l);
+            if (idx < 0) idx = psfm_key_idx(psfm_key_at(keys, id, use32), shift_b);
+            const int gy = idx / GW, gx = idx - gy * GW;
+            p0 = make_double2((double)(gx * ratio), (double)(gy * ratio));   // trajectory.py:110-115
+        }
+        s_pos[tid] = p0;
+    }
+    __syncthreads();
+    const int maxlen = s_maxlen;
+    const int j = tid & (TILE_J - 1);
+    const int q = tid / TILE_J;
+    constexpr int NLD = TILE_K * TILE_J / PSFM_BLOCK;   // tile entries a thread loads per chunk
+    const int lj = s_len[j];
+    const int64_t col = s_lane[j];
+    const int bj = s_birth[j];
+    // point t >= 1 of a trajectory born at b needs the flow of step b + t - 1 (slab b + t - 1, its column)
+    float2 r[NLD];
+#pragma unroll
+    for (int u = 0; u < NLD; ++u) {
+        const int t = q + u * (PSFM_BLOCK / TILE_J);
+        r[u] = (t >= 1 && t < lj) ? dlog[(int64_t)(bj + t - 1) * cap + col] : make_float2(0.f, 0.f);
+    }
+    if (tid < TILE_J) s_off[tid] = id0 + tid < n ? psfm_track_offset(pl, off, id0 + tid, hb, hl) : 0;   // (seen behind the loop's first barrier)
+    const int kk = tid & (TILE_K - 1);
+    const int half = tid & TILE_K;              // 0 / 32: the half-wave's first lane, and the shift of its bits in a ballot
+    for (int k0 = 0; k0 < maxlen; k0 += TILE_K) {
+#pragma unroll
+        for (int u = 0; u < NLD; ++u) dtile[j][q + u * (PSFM_BLOCK / TILE_J)] = r[u];
+        __syncthreads();
+        // the next chunk's flows travel while this one is summed and written
+        if (k0 + TILE_K < maxlen) {
+#pragma unroll
+            for (int u = 0; u < NLD; ++u) {
+                const int t = k0 + TILE_K + q + u * (PSFM_BLOCK / TILE_J);
+                r[u] = (t < lj) ? dlog[(int64_t)(bj + t - 1) * cap + col] : make_float2(0.f, 0.f);
+            }
+        }
+        // sum and write: for a fixed track, TILE_K consecutive times -> contiguous run of the result
+        const int t = k0 + kk;
+        for (int jj = tid / TILE_K; jj < TILE_J; jj += PSFM_BLOCK / TILE_K) {
+            const int l = s_len[jj];
+            if (__builtin_amdgcn_ballot_w64(k0 < l) == 0ull) continue;      // (wave-uniform: neither trajectory of the wave gets this far)
+            float2 f = dtile[jj][kk];
+            if (!(t >= 1 && t < l)) f = make_float2(0.f, 0.f);
+            const double2 base = s_pos[jj];
+            const int sticky = s_sticky[jj];
+            double2 p = make_double2(base.x + psfm_gx_scan32((double)f.x), base.y + psfm_gx_scan32((double)f.y));
+            const unsigned fine = (unsigned)(__builtin_amdgcn_ballot_w64(psfm_gx_class2(f) != 0) >> half);
+            const unsigned inr = (unsigned)(__builtin_amdgcn_ballot_w64(psfm_gx_in_range(p.x, p.y) != 0) >> half);
+            const int par = psfm_gx_chunk_parallel(sticky, fine == 0xffffffffu, inr == 0xffffffffu);
+#ifdef PSFM_GX_COUNT
+            if (kk == 0 && k0 < l) { atomicAdd(&psfm_gx_counts[0], 1ull); if (!par) atomicAdd(&psfm_gx_counts[1], 1ull); }
+#endif
+            if (__builtin_amdgcn_ballot_w64(!par) != 0ull) {
+                // the loop's order: every lane of the half-wave walks the chunk and keeps the position of its own time
+                double2 run = base, mine = base;
+                for (int s = 0; s < TILE_K; ++s) {
+                    const float fx = __shfl(f.x, s, TILE_K), fy = __shfl(f.y, s, TILE_K);
+                    run.x = run.x + (double)fx; run.y = run.y + (double)fy;
+                    if (s == kk) mine = run;
+                }
+                if (!par) p = mine;
+            }
+            if (t < l) out[s_off[jj] + t] = p;
+            if (kk == TILE_K - 1) { s_pos[jj] = p; s_sticky[jj] = par ? 0 : 1; }
         }
         __syncthreads();
     }
@@ -524,12 +669,16 @@ static psfm_status psfm_finalize_sorted(psfm_ctx* c, const PsfmTrackDims& d, con
     c->res_n_points = npts;
     // transpose the frame-major log into the id-ordered CSR
     if ((st = c->res_xy.ensure(sizeof(double2) * (size_t)(npts > 0 ? npts : 1))) != PSFM_OK) return st;
-    if (delta_log)
-        hipLaunchKernelGGL(psfm_gather_delta_kernel, dim3((unsigned)((n + TILE_J - 1) / TILE_J)), dim3(PSFM_BLOCK), 0, s,
-                           c->log.as<float2>(), d.cap, c->sort_lanes.as<int>(), c->res_birth.as<int>(),
+    c->fin_gather = 0;
+    if (delta_log) {
+        static const int gather_on = getenv("PSFM_FIN_GATHER") ? atoi(getenv("PSFM_FIN_GATHER")) : 1;   // 0: the serial kernel (A/B, tests)
+        const int gx = psfm_gx_form(gather_on, d.H, d.W);
+        hipLaunchKernelGGL(gx ? psfm_gather_delta2_kernel : psfm_gather_delta_kernel, dim3((unsigned)((n + TILE_J - 1) / TILE_J)),
+                           dim3(PSFM_BLOCK), 0, s, c->log.as<float2>(), d.cap, c->sort_lanes.as<int>(), c->res_birth.as<int>(),
                            c->res_len.as<int>(), c->res_off.as<int64_t>(), n, (const void*)c->sort_keys.p, fmt.use32,
                            d.shift_b, d.GW, d.ratio, c->res_xy.as<double2>(), pl);
-    else
+        c->fin_gather = gx ? 2 : 1;
+    } else
         hipLaunchKernelGGL(psfm_gather_kernel, dim3((unsigned)((n + TILE_J - 1) / TILE_J)), dim3(PSFM_BLOCK), 0, s,
                            c->log.as<double2>(), d.cap, c->sort_lanes.as<int>(), c->res_birth.as<int>(),
                            c->res_len.as<int>(), c->res_off.as<int64_t>(), n, c->res_xy.as<double2>(), pl);

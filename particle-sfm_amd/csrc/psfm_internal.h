@@ -170,6 +170,7 @@ struct psfm_ctx {
     int fin_sort_form = 0, fin_offsets_form = 0;   // what the last finalize ran: sort_form / offsets_form of its plan (psfm_fin_form,
                                                    // psfm_finalize_plan.h), 0 until that step was reached (psfm_ctx_get_finalize_forms)
     int fin_placed = 0;                            // ... and whether its records were placed by birth order and sorted in one pass (psfm_place.h)
+    int fin_gather = 0;                            // ... and its gather from the flow log: 0 none (position log), 1 serial sums, 2 blocked sums (psfm_gather_exact.h)
     PsfmBuf res_birth, res_len, res_off, res_xy;
     int64_t res_n_traj = 0, res_n_points = 0;
     int res_n_flows = 0;           // flows of the sequence the result came from (psfm_result_keys checks its packed key)

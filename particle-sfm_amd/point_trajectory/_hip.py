@@ -42,6 +42,7 @@ EXPORTS = [
     "psfm_track_queries_batch", "psfm_query_batch_census",
     "psfm_track_queries_optimize_batch", "psfm_query_pc_batch_census",
     "psfm_ctx_set_batch_redo", "psfm_connect_batch_census", "psfm_ctx_set_frame_size",
+    "psfm_ctx_get_finalize_gather",
 ]
 
 
@@ -102,6 +103,7 @@ def lib():
     L.psfm_sort_records64.argtypes = [vp, vp, vp, i64, i32, vp]
     L.psfm_ctx_get_finalize_forms.argtypes = [vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]
     L.psfm_ctx_get_finalize_placed.argtypes = [vp, ctypes.POINTER(ctypes.c_int32)]
+    L.psfm_ctx_get_finalize_gather.argtypes = [vp, ctypes.POINTER(ctypes.c_int32)]
     L.psfm_track.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, ctypes.POINTER(TrackInfo), vp]
     L.psfm_connect.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, vp, vp, ctypes.POINTER(TrackInfo), vp]
     L.psfm_connect_batch.argtypes = [ctypes.POINTER(vp), i32, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp),
@@ -314,6 +316,14 @@ class Context:
         persistent frame loop, 32-bit keys, at most 255 flows; PSFM_FIN_PLACE=0 turns it off), else 0.  Same bytes either way."""
         a = ctypes.c_int32()
         check(lib().psfm_ctx_get_finalize_placed(self._h, ctypes.byref(a)))
+        return int(a.value)
+
+    def finalize_gather(self):
+        """How the last id assignment of this context summed the flow log into positions: 0 it had a position log (no sums), 1 one
+        thread per trajectory in the loop's order, 2 blocked sums under the chunk rule of csrc/psfm_gather_exact.h (after the
+        persistent frame loop, frames up to 3840 pixels a side; PSFM_FIN_GATHER=0 keeps 1).  Same bytes either way."""
+        a = ctypes.c_int32()
+        check(lib().psfm_ctx_get_finalize_gather(self._h, ctypes.byref(a)))
         return int(a.value)
 
     def query_batch_census(self):
