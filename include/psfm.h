@@ -18,6 +18,8 @@
  *   psfm_connect_batch      the same for a batch of sequences: the loop of run_particlesfm.py:168-176
  *   psfm_result_*           the list of Trajectory objects those functions return and the
  *                           id / min-length rule of main_connect_point_trajectories.py:56-60
+ *   psfm_result_set         the files the reference's stages hand over (np.load(track.npy) in motion_seg/load_cut_seq.py:46,
+ *   psfm_load_track_npy     sfm/matches_from_flow.py:56): a trajectory set from elsewhere as the context's result
  *   psfm_traj_augment       motion_seg/core/network/traj_oa_depth.py:72-114 augment_traj() (the classifier's 10-channel input)
  *   psfm_traj_encode        motion_seg/core/network/traj_oa_depth.py:25-60 pt_transformer.forward() (joint_encoder, eval mode)
  *   psfm_traj_decode        motion_seg/core/network/oanet.py:13-206 OANBlock.forward() (traj_oa_depth.decoder, eval mode),
@@ -518,6 +520,36 @@ psfm_status psfm_result_solve_stats(psfm_ctx* ctx, psfm_solve_stats* stats_host,
 psfm_status psfm_result_filter(psfm_ctx* ctx, int traj_min_len, int64_t* n_traj_host, int64_t* n_points_host, void* stream);
 psfm_status psfm_result_filtered_copy(psfm_ctx* ctx, int32_t* ids_host, int32_t* birth_host, int32_t* len_host,
                                       int64_t* off_host, double* xy_host, void* stream);
+
+/* A trajectory set from elsewhere -- yesterday's track.npy, the reference's CPU stage, another tracker -- becomes the context's
+ * result, so that every consumer of a result (the filter, the window samplers, the label merge, the match tables, the database
+ * rows, ground-truth scoring) runs on it as on a tracker's.  The arrays are a saved set as psfm_result_filtered_copy returns it,
+ * without `off` (derived from len): trajectory i has id ids[i], frames birth[i] .. birth[i] + len[i] - 1 and its points in xy in
+ * that order; each pointer HOST or DEVICE (the direction follows from the pointer).
+ * The result is a CSR in which index == id, so the set is expanded to *n_result_host = ids[n_traj - 1] + 1 entries: an id the set
+ * does not hold becomes an entry with len = 0, birth = 0 and no points (the file does not say what it was, only that it was not
+ * saved); xy is taken as it is.  psfm_result_filter(ctx, 1) then reproduces the given set byte for byte, psfm_result_filter(ctx, m)
+ * its trajectories of length >= m.  On such a result psfm_result_filter(_batch) and psfm_window_sample(_batch) refuse
+ * traj_min_len < 1 (PSFM_ERR_ARG) and psfm_result_keys refuses it (no birth grid index); a live label merge and a sampler plan are
+ * void.  The next tracker call replaces it like any result.
+ * PSFM_ERR_ARG, with the lowest bad trajectory index named in psfm_last_error() and the previous result and saved set intact:
+ * negative sizes, a NULL array that is not empty, ids not strictly ascending or outside [0, 2^28), len < 1, birth < 0,
+ * birth + len > 2^30, sum(len) != n_points.  n_traj == 0 is legal and leaves an empty result.  Coordinates are not looked at.
+ * Synchronises `stream`; two host synchronisations (the verdict, the point total). */
+psfm_status psfm_result_set(psfm_ctx* ctx, int64_t n_traj, int64_t n_points, const int32_t* ids, const int32_t* birth,
+                            const int32_t* len, const double* xy, int64_t* n_result_host, void* stream);
+
+/* psfm_result_set for a track.npy that save_track_npy(layout="reference") of this package wrote, straight from the file: the
+ * 64-byte footer behind the pickle names the raw f64 point bytes and the fixed-size records (one per trajectory); the records go
+ * through the context's ring of pinned buffers (psfm_load_flo_stack's) into a device workspace and are decoded there, the set is
+ * validated and expanded as by psfm_result_set, and only then the point bytes are streamed into the result.  The pickle is never
+ * interpreted: rec_template (rec_size bytes, 63 as the writer stands and at most 68: the record with zeroed fields) and field_at (offsets of the six 4-byte fields
+ * id, b, b + n, s, e, n) come from the writer's own definition.  n_threads reader threads (1 .. 32).
+ * PSFM_ERR_ARG with the context untouched: a missing, short or foreign file, a footer that fails a check, a record that differs
+ * from the template or whose fields disagree (the lowest such trajectory is named), a set psfm_result_set would refuse.  A read
+ * error while the points stream leaves an EMPTY result (the previous one is gone by then; the message says so). */
+psfm_status psfm_load_track_npy(psfm_ctx* ctx, const char* path, const uint8_t* rec_template, int rec_size, const int32_t* field_at,
+                                int n_threads, int64_t* n_traj_host, int64_t* n_points_host, int64_t* n_result_host, void* stream);
 
 /* The motion-segmentation window tensors (motion_seg/load_cut_seq.py:60-89) from the device-resident result of the last
  * psfm_track / psfm_connect -- TrajectorySet::sample_inside_window (optimize/src/trajectory_base.cpp:127-185) for the

@@ -15,7 +15,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libpsfm_hip.so")
-SOURCES = ["psfm_api.hip", "psfm_track.hip", "psfm_persist.hip", "psfm_finalize.hip", "psfm_place.hip", "psfm_sort.hip", "psfm_sort64.hip", "psfm_solver.hip", "psfm_solver_fused.hip", "psfm_solver_batch.hip", "psfm_solver_batch_mb.hip", "psfm_window.hip", "psfm_window_batch.hip", "psfm_matches.hip", "psfm_matches_batch.hip", "psfm_shard.hip", "psfm_batch.hip", "psfm_ingest.hip", "psfm_labels.hip", "psfm_augment.hip", "psfm_encoder.hip", "psfm_decoder.hip", "psfm_ground_truth.hip", "psfm_database.hip", "psfm_sparse_depth.hip", "psfm_motion_boundary.hip", "psfm_depth_display.hip", "psfm_query.hip", "psfm_query_pc.hip", "psfm_query_batch.hip", "psfm_solver_multi.hip", "psfm_query_pc_batch.hip"]
+SOURCES = ["psfm_api.hip", "psfm_track.hip", "psfm_persist.hip", "psfm_finalize.hip", "psfm_place.hip", "psfm_sort.hip", "psfm_sort64.hip", "psfm_solver.hip", "psfm_solver_fused.hip", "psfm_solver_batch.hip", "psfm_solver_batch_mb.hip", "psfm_window.hip", "psfm_window_batch.hip", "psfm_matches.hip", "psfm_matches_batch.hip", "psfm_shard.hip", "psfm_batch.hip", "psfm_ingest.hip", "psfm_labels.hip", "psfm_augment.hip", "psfm_encoder.hip", "psfm_decoder.hip", "psfm_ground_truth.hip", "psfm_database.hip", "psfm_sparse_depth.hip", "psfm_motion_boundary.hip", "psfm_depth_display.hip", "psfm_query.hip", "psfm_query_pc.hip", "psfm_query_batch.hip", "psfm_solver_multi.hip", "psfm_query_pc_batch.hip", "psfm_result_set.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
          "-Wall", "-Wno-unused-function", "-Wno-unused-result",

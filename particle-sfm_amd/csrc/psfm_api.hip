@@ -181,7 +181,8 @@ extern "C" psfm_status psfm_ctx_destroy(psfm_ctx* c)
                        &c->handoff, &c->place_tab, &c->seg_info, &c->seg_table, &c->persist_bar, &c->batch_tab, &c->batch_ws, &c->batch_fc, &c->win_ws, &c->winb_ws, &c->flt_ids, &c->flt_birth, &c->flt_len, &c->flt_off, &c->flt_xy,
                        &c->mt_kp_off, &c->mt_q, &c->mt_pts, &c->mt_kp_ind, &c->mt_kp_xy, &c->mt_moff, &c->mt_keys, &c->mt_rows, &c->mt_gid, &c->mt_pairs, &c->mtb_tab, &c->mtb_sizes, &c->mtb_len,
                        &c->lb_state, &c->lb_first, &c->lb_flag, &c->lb_ws, &c->lb_ids, &c->lb_off, &c->lb_frames, &c->lb_xy, &c->lb_labels, &c->gt_flag, &c->kill, &c->batch_km,
-                       &c->db_kp, &c->db_pairs, &c->db_rows, &c->db_ws, &c->sd_ws, &c->dd_ws, &c->dd_comp, &c->qr_ws, &c->qb_tab, &c->qb_ws, &c->qpb_tab, &c->qpb_ws, &c->qpb_owner};
+                       &c->db_kp, &c->db_pairs, &c->db_rows, &c->db_ws, &c->sd_ws, &c->dd_ws, &c->dd_comp, &c->qr_ws, &c->qb_tab, &c->qb_ws, &c->qpb_tab, &c->qpb_ws, &c->qpb_owner,
+                       &c->rs_ws, &c->rs_rec, &c->rs_birth, &c->rs_len, &c->rs_off, &c->rs_xy};
     for (auto b : bufs) b->release();
     for (hipEvent_t e : c->sd_events) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->dd_events) if (e) (void)hipEventDestroy(e);

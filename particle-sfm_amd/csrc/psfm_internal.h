@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
+#include <functional>
 #include <shared_mutex>
 #include <string>
 #include <vector>
@@ -176,6 +177,11 @@ struct psfm_ctx {
     int res_n_flows = 0;           // flows of the sequence the result came from (psfm_result_keys checks its packed key)
     bool res_is_query = false;     // the result is psfm_track_queries': trajectory i is query i, no birth grid index (psfm_result_keys
                                    // refuses it); cleared by every other entry point that replaces the result
+    bool res_is_set = false;       // the result is psfm_result_set's / psfm_load_track_npy's: a set from elsewhere expanded to index == id,
+                                   // ids it does not hold as entries with len = 0 -- no birth grid index (psfm_result_keys refuses it), and
+                                   // the filter and the samplers refuse traj_min_len < 1 on it; cleared like res_is_query
+    PsfmBuf rs_ws, rs_rec;         // psfm_result_set.hip: verdict block | the staged ids, births, lengths, record slices; a file's records
+    PsfmBuf rs_birth, rs_len, rs_off, rs_xy;   // ... the next result while it is validated: exchanged with res_* behind a clean verdict
     PsfmBuf qr_ws;                 // psfm_track_queries (psfm_query.hip): first refused query | lengths per direction | scan storage
                                    // (psfm_track_queries_optimize, psfm_query_pc.hip: ... | rows per wave | the rows of a frame's solve)
     // psfm_track_queries_batch (psfm_query_batch.hip), this context as the call's owner: the table of sequences | the block prefix |
@@ -303,6 +309,16 @@ struct psfm_ctx {
 static inline PsfmShard* psfm_host_shards(const psfm_ctx* c) { return (PsfmShard*)((char*)c->host_pinned + 512); }
 static inline PsfmSolveCtrl* psfm_host_solve_ctrl(const psfm_ctx* c) { return (PsfmSolveCtrl*)(psfm_host_shards(c) + PSFM_NSHARD); }
 
+// A result that came from psfm_result_set / psfm_load_track_npy holds entries with len = 0 for the ids the set does not name; the
+// filter and the samplers skip them with the arithmetic they have as long as traj_min_len >= 1, so they refuse anything below.
+static inline bool psfm_set_result_refuses(const psfm_ctx* c, int traj_min_len, const char* who)
+{
+    if (!c->res_is_set || traj_min_len >= 1) return false;
+    psfm_set_error("%s: traj_min_len=%d on a result that psfm_result_set / psfm_load_track_npy put in (ids the set does not hold are "
+                   "entries of length 0: traj_min_len must be >= 1)", who, traj_min_len);
+    return true;
+}
+
 // What a call that runs the frame recurrence (psfm_track / psfm_connect, psfm_connect_batch per sequence) starts from: no solve
 // statistics, no result, no solves counted.  pc_persist_ok: the call has the device to itself (or a resident budget).
 static inline void psfm_call_begin(psfm_ctx* c, int n_flows, bool pc_persist_ok)
@@ -311,6 +327,7 @@ static inline void psfm_call_begin(psfm_ctx* c, int n_flows, bool pc_persist_ok)
     c->res_n_traj = c->res_n_points = 0;
     c->res_n_flows = n_flows;
     c->res_is_query = false;
+    c->res_is_set = false;
     c->pc_persist_ok = pc_persist_ok;
     c->pc_giveups = 0;
     c->n_fused_ok = c->n_fused_redone = c->n_chain = 0;
@@ -401,6 +418,16 @@ psfm_status psfm_track_alloc(psfm_ctx* c, const PsfmTrackDims& d);
 psfm_status psfm_launch_track_init(psfm_ctx* c, const PsfmTrackDims& d, hipStream_t s);
 psfm_status psfm_launch_chain_step(psfm_ctx* c, const PsfmTrackDims& d, const float* flow, const uint8_t* occ,
                                    int frame, bool optimize, hipStream_t s);
+
+// ---- the ingest pipeline (psfm_ingest.hip): reader threads -> the context's ring of pinned buffers -> copies on its copy streams ----
+// psfm_ring_stream: item i of n is read by fill(i, slot, &bytes, err) into a slot of `slot_bytes` bytes and copied to dst(i); returns
+// when the last copy has completed.  PSFM_ERR_ARG: a fill returned false, its message is in `err` (the caller words the error).  The
+// caller holds the device gate.  psfm_ring_stream_file: a byte range of an open file, in 8 MiB chunks.
+psfm_status psfm_ring_stream(psfm_ctx* c, const char* who, int64_t n, size_t slot_bytes, int n_threads, hipStream_t s,
+                             const std::function<bool(int64_t, char*, size_t*, std::string&)>& fill,
+                             const std::function<char*(int64_t)>& dst, std::string& err);
+psfm_status psfm_ring_stream_file(psfm_ctx* c, const char* who, int fd, int64_t file_off, size_t nbytes, char* dst_dev, int n_threads,
+                                  hipStream_t s, std::string& err);
 
 // ---- motion boundary (psfm_motion_boundary.hip) ----------------------------------------------
 // out[f,y,x] = motion-boundary bit of pixel (x, y) of flow map f: 0/1 when occ == NULL, else (occ != 0) | mb << 1 (the kill map)

@@ -520,6 +520,7 @@ extern "C" psfm_status psfm_result_filter_batch(psfm_ctx* const* ctxs, int n_seq
     psfm_status st;
     if ((st = pmb_check_ctxs(who, ctxs, n_seq)) != PSFM_OK) return st;
     if (!n_traj_host || !n_points_host) { psfm_set_error("%s: NULL argument", who); return PSFM_ERR_ARG; }
+    for (int b = 0; b < n_seq; ++b) if (psfm_set_result_refuses(ctxs[b], traj_min_len, who)) return PSFM_ERR_ARG;
     const int B = n_seq;
     int64_t n[PSFM_MTB_MAX], k[PSFM_MTB_MAX], k1[PSFM_MTB_MAX], kw[PSFM_MTB_MAX], base[PSFM_MTB_MAX + 1];
     int64_t N = 0;

@@ -227,6 +227,7 @@ extern "C" psfm_status psfm_track_queries(psfm_ctx* c, const float* flows_f, con
     c->res_n_traj = c->res_n_points = 0;
     c->res_n_flows = n_flows;
     c->res_is_query = true;
+    c->res_is_set = false;
     const size_t nq1 = Q > 0 ? Q : 1;
     if ((st = c->log.ensure(sizeof(double2) * (size_t)(n_flows + 1) * nq1)) != PSFM_OK) return st;
     if ((st = c->res_birth.ensure(sizeof(int) * nq1)) != PSFM_OK) return st;

@@ -333,6 +333,7 @@ psfm_status psfm_qb_run(psfm_ctx* const* ctxs, int n_seq, const float* const* fl
         c->res_n_traj = c->res_n_points = 0;
         c->res_n_flows = n_flows[i];
         c->res_is_query = true;
+        c->res_is_set = false;
     }
     for (int i = 0; i < n_seq; ++i) {
         psfm_ctx* c = ctxs[i];

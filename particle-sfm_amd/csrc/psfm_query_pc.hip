@@ -165,6 +165,7 @@ extern "C" psfm_status psfm_track_queries_optimize(psfm_ctx* c, const float* flo
     c->res_n_traj = c->res_n_points = 0;
     c->res_n_flows = n_flows;
     c->res_is_query = true;
+    c->res_is_set = false;
     c->pc_persist_ok = gate.exclusive || c->resident_budget > 0;
     c->pc_giveups = 0;
     c->n_resident = c->n_iter_launches = 0;

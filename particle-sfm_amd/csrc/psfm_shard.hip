@@ -72,6 +72,7 @@ extern "C" psfm_status psfm_shard_begin(psfm_ctx* c, int n_flows, int h, int w, 
     c->res_n_traj = c->res_n_points = 0;
     c->res_n_flows = n_flows;
     c->res_is_query = false;
+    c->res_is_set = false;
     *(int32_t*)((char*)c->host_pinned + c->host_pinned_bytes - 64) = 0;
     delete c->shard_dims;
     c->shard_dims = new PsfmTrackDims(d);
@@ -478,6 +479,10 @@ extern "C" psfm_status psfm_result_keys(psfm_ctx* c, int ratio, int w, int64_t* 
     const int64_t n = c->res_n_traj;
     if (c->res_is_query) {     // (psfm_track_queries: a query has no birth grid index to build the key from)
         psfm_set_error("psfm_result_keys: the result holds query tracks (psfm_track_queries), which have no birth grid index");
+        return PSFM_ERR_ARG;
+    }
+    if (c->res_is_set) {       // (psfm_result_set / psfm_load_track_npy: a set from elsewhere, entries of length 0 among it)
+        psfm_set_error("psfm_result_keys: the result is a trajectory set from elsewhere (psfm_result_set), which has no birth grid index");
         return PSFM_ERR_ARG;
     }
     if (c->res_n_flows + 2 >= (1 << PSFM_KEY_TIME_BITS)) {     // (the result of a plain psfm_track of a longer sequence)

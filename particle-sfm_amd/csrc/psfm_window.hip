@@ -97,6 +97,7 @@ extern "C" psfm_status psfm_window_sample(psfm_ctx* c, int frame0, int n_frames,
                        (long long)max_num_tracks, (long long)capacity);
         return PSFM_ERR_ARG;
     }
+    if (psfm_set_result_refuses(c, traj_min_len, "psfm_window_sample")) return PSFM_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     const int64_t n = c->res_n_traj;
     *k_host = 0;
@@ -198,6 +199,7 @@ __global__ __launch_bounds__(PW_BLOCK) void psfm_filter_copy_kernel(const int* _
 extern "C" psfm_status psfm_result_filter(psfm_ctx* c, int traj_min_len, int64_t* n_traj_host, int64_t* n_points_host, void* stream)
 {
     if (!c || !n_traj_host || !n_points_host) { psfm_set_error("psfm_result_filter: NULL argument"); return PSFM_ERR_ARG; }
+    if (psfm_set_result_refuses(c, traj_min_len, "psfm_result_filter")) return PSFM_ERR_ARG;      // (the saved set stays as it was)
     PSFM_HIP(hipSetDevice(c->device));
     PsfmGate gate(c->device, 0);
     hipStream_t s = (hipStream_t)stream;

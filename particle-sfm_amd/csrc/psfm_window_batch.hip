@@ -250,6 +250,7 @@ extern "C" psfm_status psfm_window_sample_batch(psfm_ctx* c, int n_win, const in
             psfm_set_error("psfm_window_sample_batch: window %d: frame0=%d n_frames=%d leaves the 32-bit frame range", b, frame0[b], n_frames);
             return PSFM_ERR_ARG;
         }
+    if (psfm_set_result_refuses(c, traj_min_len, "psfm_window_sample_batch")) return PSFM_ERR_ARG;
     PSFM_HIP(hipSetDevice(c->device));
     PsfmGate gate(c->device, 0);
     hipStream_t s = (hipStream_t)stream;

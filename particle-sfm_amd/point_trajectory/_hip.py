@@ -43,6 +43,7 @@ EXPORTS = [
     "psfm_track_queries_optimize_batch", "psfm_query_pc_batch_census",
     "psfm_ctx_set_batch_redo", "psfm_connect_batch_census", "psfm_ctx_set_frame_size",
     "psfm_ctx_get_finalize_gather",
+    "psfm_result_set", "psfm_load_track_npy",
 ]
 
 
@@ -138,6 +139,8 @@ def lib():
     L.psfm_solver_launches.argtypes = [vp, ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(i64)]
     L.psfm_result_filter.argtypes = [vp, i32, ctypes.POINTER(i64), ctypes.POINTER(i64), vp]
     L.psfm_result_filtered_copy.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.psfm_result_set.argtypes = [vp, i64, i64, vp, vp, vp, vp, ctypes.POINTER(i64), vp]
+    L.psfm_load_track_npy.argtypes = [vp, ctypes.c_char_p, vp, i32, vp, i32, ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(i64), vp]
     L.psfm_window_sample.argtypes = [vp, i32, i32, i32, i32, i64, ctypes.c_uint64, i32, i32, i32, i32, i64, vp, vp, vp, vp,
                                      ctypes.POINTER(i64), vp]
     L.psfm_traj_augment.argtypes = [vp, vp, vp, vp, i64, i32, i32, i32, vp, vp, vp]
@@ -340,6 +343,46 @@ class Context:
         a, b, c = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
         check(lib().psfm_query_pc_batch_census(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
         return {"launches_fixed": int(a.value), "launches_iter": int(b.value), "host_syncs": int(c.value)}
+
+    def set_result(self, ids, birth, length, xy):
+        """psfm_result_set: a trajectory set from elsewhere becomes this context's result.  ids / birth / length (n,) and xy
+        (n_points, 2): NumPy arrays (host) or torch tensors (host or device), converted to i32 / f64 when they are not; trajectory i
+        holds frames birth[i] .. birth[i] + length[i] - 1, ids ascend strictly.  The result has ids[-1] + 1 entries -- index == id,
+        ids the set does not name are entries of length 0 -- and that count is returned.  PsfmError (status PSFM_ERR_ARG, the lowest bad
+        index in the message) leaves the context as it was."""
+        import numpy as np
+        import torch
+
+        def arr(a, np_dt, t_dt, shape):
+            if isinstance(a, torch.Tensor):
+                t = a.reshape(shape).to(t_dt).contiguous()
+                return t, ctypes.c_void_p(t.data_ptr() if t.numel() else 0)
+            h = np.ascontiguousarray(np.asarray(a).reshape(shape), dtype=np_dt)
+            return h, ctypes.c_void_p(h.ctypes.data if h.size else 0)
+        keep = [arr(ids, np.int32, torch.int32, (-1,)), arr(birth, np.int32, torch.int32, (-1,)), arr(length, np.int32, torch.int32, (-1,)),
+                arr(xy, np.float64, torch.float64, (-1, 2))]
+        n = int(keep[0][0].shape[0])
+        if int(keep[1][0].shape[0]) != n or int(keep[2][0].shape[0]) != n:
+            raise ValueError("set_result: ids, birth and length must have one entry per trajectory")
+        n_result = ctypes.c_int64(0)
+        check(lib().psfm_result_set(self._h, n, int(keep[3][0].shape[0]), keep[0][1], keep[1][1], keep[2][1], keep[3][1],
+                                    ctypes.byref(n_result), current_stream_ptr(self.device)))
+        return int(n_result.value)
+
+    def load_track_npy(self, path, threads=4):
+        """psfm_load_track_npy: a track.npy that save_track_npy(layout="reference") wrote, from the file into this context's result
+        (records and points through the pinned ring, decoded and validated on the device).  Returns (n_traj, n_points, n_result).
+        PsfmError with status PSFM_ERR_ARG: not such a file, or one that fails a check -- the context is as it was, except behind a
+        read error while the points stream (an empty result; the message says so)."""
+        import numpy as np
+        from . import reference_pickle
+        rec, at = reference_pickle._record_template()
+        tmpl = np.frombuffer(rec, np.uint8).copy()
+        field_at = np.asarray([at[k] for k in ("id", "b", "bn", "s", "e", "n")], np.int32)
+        n, p, r = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        check(lib().psfm_load_track_npy(self._h, os.fsencode(str(path)), tmpl.ctypes.data, len(rec), field_at.ctypes.data, int(threads),
+                                        ctypes.byref(n), ctypes.byref(p), ctypes.byref(r), current_stream_ptr(self.device)))
+        return int(n.value), int(p.value), int(r.value)
 
     def set_sparse_depth(self, budget_bytes=1 << 30, timing=False):
         """psfm_sfm.convert: bytes of depth maps + winner maps (12 per pixel) one psfm_sparse_depth call may take (0: no limit; one

@@ -114,7 +114,7 @@ def dump(fp, ts):
     j = i + len(mark)
     assert stream[j:j + 1] == b"q" and stream.count(mark) == 1, "unexpected pickle layout of the template"
     prefix, suffix = stream[:i], stream[j + 2:]
-    # The records (66 bytes per trajectory, filled in with NumPy) are built on a helper thread while this one writes the point array --
+    # The records (63 bytes per trajectory, filled in with NumPy) are built on a helper thread while this one writes the point array --
     # the bulk of the file, a single write() that spends its time in the kernel's page-cache copy with the GIL released.
     rec, at = _record_template()
     R = len(rec)

@@ -293,6 +293,83 @@ def load_track_npy(path):
     return reference_pickle.load(path)
 
 
+def _trajectory_set_to_device(self, ctx=None):
+    """TrajectorySet.to_device(ctx=None): this set as the RESULT of a context (psfm_result_set), so that the device consumers of a
+    tracker's result -- the window sampler, the label merge, the match tables, the database rows -- run on it.  Trajectories go in
+    ascending id order, as the reference's std::map iterates; labels are not carried (a result has none).  A trajectory whose
+    frame_ids are not consecutive raises ValueError naming its id: a result holds frames birth .. birth + len - 1, sets with gaps
+    enter as a labelled set (psfm_motion_seg.merge_labels.set_labelled).  Returns the context (default: the calling thread's)."""
+    if self._csr is not None and self._map is None:
+        ids, birth, length, off, xy, _ = self._csr
+        ids, birth, length = np.asarray(ids, np.int64), np.asarray(birth, np.int32), np.asarray(length, np.int32)
+        if len(ids) > 1 and np.any(ids[1:] <= ids[:-1]):
+            order = np.argsort(ids, kind="stable")
+            n_of = length[order].astype(np.int64)
+            pts = np.repeat(np.asarray(off[:-1], np.int64)[order], n_of) + (np.arange(int(n_of.sum())) - np.repeat(np.cumsum(n_of) - n_of, n_of))
+            ids, birth, length, xy = ids[order], birth[order], length[order], np.asarray(xy)[pts]
+    else:
+        keys = sorted(self._map)
+        ids = np.asarray(keys, np.int64)
+        birth, length, locs = np.zeros(len(keys), np.int32), np.zeros(len(keys), np.int32), []
+        for j, k in enumerate(keys):
+            t = self._map[k]
+            times = np.fromiter(t._times, np.int64, count=len(t._times))[:len(t._xys)]
+            if len(times) == 0 or np.any(times != times[0] + np.arange(len(times))):
+                raise ValueError("TrajectorySet.to_device: trajectory %d has no points or frame_ids that are not consecutive "
+                                 "(a result holds frames birth .. birth + len - 1; psfm_labels_set takes sets with gaps)" % int(k))
+            birth[j], length[j] = times[0], len(times)
+            locs.append(np.asarray(t._xys, dtype=np.float64).reshape(-1, 2))
+        xy = np.concatenate(locs) if locs else np.zeros((0, 2))
+    if len(ids) and (int(ids[0]) < 0 or int(ids[-1]) >= 1 << 28):
+        raise ValueError("TrajectorySet.to_device: ids must lie in [0, 2^28)")
+    ctx = ctx or _hip.context()
+    ctx.set_result(ids.astype(np.int32), birth, length, xy)
+    return ctx
+
+
+# The container class mirrors the reference's pybind module and knows nothing of contexts; its device entry is attached here, where
+# the package's other context routes live (importing point_trajectory, or anything inside it, imports this module).
+particlesfm.TrajectorySet.to_device = _trajectory_set_to_device
+
+
+def load_track_npy_device(path, ctx=None, threads=4):
+    """track.npy -> a context, for the device consumers of a stage that starts from a file.  Returns (ctx, kind, sizes):
+      kind "set"       the file held a TrajectorySet: it is the context's RESULT now (psfm_result_set: index == id, ids the file does
+                       not hold are entries of length 0; psfm_result_filter(ctx, 1) gives the file's set back).  A file this package
+                       wrote in the reference layout goes from the file into HBM (psfm_load_track_npy, `threads` reader threads); when
+                       that call refuses it (PSFM_ERR_ARG: no footer -- the csr layout, a file the reference's own module pickled --
+                       or a footer that fails a check) the file goes through load_track_npy and TrajectorySet.to_device.
+                       sizes = {"n_traj", "n_points", "n_result", "route": "file" | "host"}
+      kind "labelled"  the file held the plain dict stage 2 writes: flattened in the dict's order, it is the context's LABELLED set
+                       (psfm_labels_set).  sizes = {"n_traj", "n_points", "route": "host"}
+    sizes["true_labels"] (kind "set", host route): the file's set carries True labels, which a result cannot hold (they are dropped).
+    ctx=None takes the calling thread's context, the one run_connect uses by default: the result (or labelled set) a tracker left
+    there is REPLACED without notice -- pass a context of your own (_hip.Context(device)) to keep it."""
+    ctx = ctx or _hip.context()
+    try:
+        n, p, r = ctx.load_track_npy(path, threads)
+        return ctx, "set", {"n_traj": n, "n_points": p, "n_result": r, "route": "file"}
+    except _hip.PsfmError as e:
+        if e.status != _hip.PSFM_ERR_ARG:
+            raise
+    obj = load_track_npy(path)
+    if isinstance(obj, particlesfm.TrajectorySet):
+        obj.to_device(ctx)
+        n_points = int(obj._csr[3][-1]) if obj._map is None else sum(len(t._xys) for t in obj._map.values())
+        ids = obj._csr[0] if obj._map is None else list(obj._map)
+        if obj._map is None:
+            true_labels = obj._csr[5] is not None and bool(np.any(obj._csr[5]))
+        else:
+            true_labels = any(t._labels is not None and any(t._labels) for t in obj._map.values())
+        return ctx, "set", {"n_traj": len(obj), "n_points": n_points, "n_result": (int(max(ids)) + 1) if len(obj) else 0, "route": "host",
+                            "true_labels": true_labels}
+    if isinstance(obj, dict):
+        from psfm_motion_seg.merge_labels import set_labelled
+        n, p = set_labelled(ctx, obj)
+        return ctx, "labelled", {"n_traj": n, "n_points": p, "route": "host"}
+    raise TypeError("load_track_npy_device: %s holds a %s, neither a TrajectorySet nor a labelled dict" % (path, type(obj).__name__))
+
+
 def _as_device_stack(maps, dtype, trailing):
     """list of (H,W[,2]) arrays | (n,H,W[,2]) array/tensor -> contiguous device tensor."""
     import torch

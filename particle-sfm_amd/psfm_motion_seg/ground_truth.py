@@ -69,6 +69,16 @@ def frame_counts_device(masks_u8, frame_ids=None, xy=None, labels=None, table=No
     return counts
 
 
+def frame_counts_file_device(track_npy, masks_u8, table=None, ctx=None):
+    """frame_counts_device for a labelled track.npy (the dict stage 2 writes): merge_labels.set_labelled, then the counts.  ctx=None: the
+    calling thread's context, whose labelled set is replaced."""
+    from point_trajectory import _hip
+    from .merge_labels import set_labelled
+    ctx = ctx or _hip.context()
+    set_labelled(ctx, np.load(track_npy, allow_pickle=True).item())
+    return frame_counts_device(masks_u8, table=table, ctx=ctx)
+
+
 def seg_metrics_from_counts(counts):
     """(n,4) counts [tp, fp, fn, tn] -> (n,4) f64 [iou, precision, recall, f1] as seg_metrics (eval_traj_iou.py:67-76) reports them:
     iou = tp / ((tp + fp + fn) + 1e-6) (:71-73); precision, recall and F1 the binary ones of

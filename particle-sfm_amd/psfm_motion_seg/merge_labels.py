@@ -84,6 +84,30 @@ def labelled_as_dict(ids, off, frame_ids, xy, labels):
             for i in range(len(ids))}
 
 
+def set_labelled(ctx, trajectories_dict):
+    """A labelled set from elsewhere -- the dict a labelled track.npy holds, {id: {"frame_ids", "locations", "labels"}} -- becomes the
+    context's labelled set (psfm_labels_set), flattened in the dict's order: the order sfm/matches_from_flow.py:67 iterates in.  A
+    trajectory's frames may have gaps.  match_tables_labelled_device, database_tables_device and ground_truth.frame_counts_device then
+    run on it as on LabelMerger.finish()'s.  Returns (n_traj, n_points)."""
+    from point_trajectory import _hip
+    keys = list(trajectories_dict)
+    cnt = [len(trajectories_dict[k]["frame_ids"]) for k in keys]
+    off = np.zeros(len(keys) + 1, np.int64)
+    np.cumsum(cnt, out=off[1:])
+    cat = lambda name, dt, shape: (np.concatenate([np.asarray(trajectories_dict[k][name]).reshape(shape).astype(dt) for k in keys])
+                                   if keys else np.zeros((0,) + shape[1:], dt))
+    ids = np.ascontiguousarray(np.asarray(keys, np.int64).astype(np.int32))
+    frames = np.ascontiguousarray(cat("frame_ids", np.int32, (-1,)))
+    xy = np.ascontiguousarray(cat("locations", np.float64, (-1, 2)))
+    labels = np.ascontiguousarray(cat("labels", bool, (-1,)).astype(np.uint8))
+    if len(xy) != int(off[-1]) or len(labels) != int(off[-1]):
+        raise ValueError("set_labelled: frame_ids, locations and labels of a trajectory must have one entry per point")
+    vp = lambda a: ctypes.c_void_p(a.ctypes.data if a.size else 0)
+    _hip.check(_hip.lib().psfm_labels_set(ctx.handle, len(keys), int(off[-1]), vp(ids), vp(off), vp(frames), vp(xy), vp(labels),
+                                          _hip.current_stream_ptr(ctx.device)))
+    return len(keys), int(off[-1])
+
+
 class LabelMerger:
     """The device path.  Construction runs psfm_labels_begin on the saved set that psfm_result_filter left in `ctx` (a later
     psfm_result_filter / psfm_track / psfm_connect on the context voids the merger: add_window and finish then raise PsfmError)."""
@@ -306,3 +330,23 @@ def label_sequences_batched(ctxs, lengths, window, raw_hw, input_size, traj_max_
     if ctxs:
         _decode_and_merge(mergers, per_ctx, dec_weights, ctxs[0], max_rows)
     return mergers
+
+
+def label_track_npy(traj_dir, output_traj_dir, length, raw_hw, input_size, enc_weights, dec_weights, depth_for_window, window=10,
+                    traj_max_num=100000, seed=0, front="window"):
+    """Stage 2 from file to file (motion_seg/main_motion_segmentation.py with the trajectories of traj_dir/track.npy): the file goes
+    into a context (point_trajectory.trajectory.load_track_npy_device), label_trajectories_batched runs on that context with
+    traj_min_len = 1 -- the file IS the saved set -- and the labelled dict is saved as output_traj_dir/track.npy, the file
+    sfm/matches_from_flow.py reads.  Depth maps stay the caller's (depth_for_window(time_idx), as everywhere else).  Returns the
+    finished merger (its labelled set stays in its context).  The file is loaded into the calling thread's context
+    (load_track_npy_device with ctx=None): whatever result a tracker left there is replaced."""
+    import os
+    from point_trajectory.trajectory import load_track_npy_device
+    ctx, kind, _ = load_track_npy_device(os.path.join(traj_dir, "track.npy"))
+    if kind != "set":
+        raise ValueError("label_track_npy: %s holds a labelled dict, not a TrajectorySet" % os.path.join(traj_dir, "track.npy"))
+    merger = label_trajectories_batched(length, window, raw_hw, input_size, traj_max_num, enc_weights, dec_weights, depth_for_window,
+                                        seed=seed, traj_min_len=1, ctx=ctx, front=front)
+    os.makedirs(output_traj_dir, exist_ok=True)
+    np.save(os.path.join(output_traj_dir, "track.npy"), merger.as_dict())
+    return merger

@@ -182,10 +182,21 @@ def write_database(database_path, image_ids, image_names, db_tables, skip_geomet
 
 
 def import_keypoints_matches(image_ids, image_dir, database_path, match_list_file, traj_dir, skip_geometric_verification=False,
-                             remove_dynamic=True):
-    """sfm/import_feature_matches.py:76-104, same arguments, on the host: track.npy -> match tables -> database tables -> rows."""
+                             remove_dynamic=True, device=False):
+    """sfm/import_feature_matches.py:76-104, same arguments, on the host: track.npy -> match tables -> database tables -> rows.
+    device=True: the file goes into a context (point_trajectory.trajectory.load_track_npy_device) and the match tables and the
+    database rows come from the device kernels (import_keypoints_matches_device); the same pair file and the same rows.  The file is
+    loaded into the calling thread's context, whose result or labelled set is replaced; a TrajectorySet file that carries True labels
+    (a result holds none) takes the host route below."""
     from point_trajectory.trajectory import load_track_npy
     image_names = sorted(os.listdir(image_dir))
+    if device:
+        from point_trajectory.trajectory import load_track_npy_device
+        ctx, kind, sizes = load_track_npy_device(os.path.join(traj_dir, "track.npy"))
+        if not (kind == "set" and sizes.get("true_labels")):
+            import_keypoints_matches_device(ctx, image_ids, image_names, database_path, match_list_file, skip_geometric_verification,
+                                            labelled=(kind == "labelled"), remove_dynamic=remove_dynamic, traj_min_len=1)
+            return
     db_id, db_pos = ids_and_positions(image_ids, image_names)
     off, frames, xy, labels = mff._flatten(load_track_npy(os.path.join(traj_dir, "track.npy")))
     tables = mff.match_tables_host(off, frames, xy, labels, len(image_names), remove_dynamic)

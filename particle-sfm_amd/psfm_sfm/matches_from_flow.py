@@ -126,11 +126,34 @@ def assemble(image_names, tables, match_list_file, as_arrays=False):
     return out
 
 
-def traj_to_matches(img_dir, traj_dir, match_list_file, remove_dynamic=True, sample_k=SAMPLE_K, as_arrays=False):
+def match_tables_file_device(track_npy, n_img, remove_dynamic=True, sample_k=SAMPLE_K, ctx=None):
+    """The match tables of a track.npy on the device: the file into a context (load_track_npy_device), then -- a TrajectorySet file --
+    psfm_result_filter(ctx, 1) and psfm_traj_to_matches (the reference iterates EVERY trajectory of the file and applies no length
+    filter there), or -- a labelled dict -- psfm_labels_to_matches.  A TrajectorySet file that carries True labels (a result holds
+    none) takes the host tables, so that remove_dynamic means what it means on the host route.  Returns (ctx, kind, tables).
+    ctx=None: the calling thread's context, whose result or labelled set is replaced (load_track_npy_device)."""
+    from point_trajectory.trajectory import load_track_npy, load_track_npy_device
+    ctx, kind, sizes = load_track_npy_device(track_npy, ctx)
+    if kind == "set" and sizes.get("true_labels"):
+        off, frames, xy, labels = _flatten(load_track_npy(track_npy))
+        return ctx, kind, match_tables_host(off, frames, xy, labels, n_img, remove_dynamic, sample_k)
+    if kind == "set":
+        return ctx, kind, match_tables_device(ctx, n_img, 1, sample_k)
+    return ctx, kind, match_tables_labelled_device(ctx, n_img, remove_dynamic, sample_k)
+
+
+def traj_to_matches(img_dir, traj_dir, match_list_file, remove_dynamic=True, sample_k=SAMPLE_K, as_arrays=False, device=False):
     """sfm/matches_from_flow.py:51-118, same arguments.  as_arrays=True keeps `.keypoints` / `.match_pairs[...]` as
     (n,2) ndarrays instead of nested lists -- the only consumer (sfm/import_feature_matches.py:82,96) wraps them in
-    np.array() anyway, and building ~1e7 two-element lists is what dominates the list form."""
+    np.array() anyway, and building ~1e7 two-element lists is what dominates the list form.
+    device=True: the file goes into a context and the tables come from the device kernels (match_tables_file_device); what is
+    returned and written is the same (a TrajectorySet file that carries True labels takes the host tables: a result has none).  The
+    file is loaded into the calling thread's context, whose result a tracker may have left there: it is replaced."""
     from point_trajectory.trajectory import load_track_npy
+    if device:
+        image_names = sorted(os.listdir(img_dir))
+        _, _, tables = match_tables_file_device(os.path.join(traj_dir, "track.npy"), len(image_names), remove_dynamic, sample_k)
+        return assemble(image_names, tables, match_list_file, as_arrays)
     trajectories = load_track_npy(os.path.join(traj_dir, "track.npy"))      # (either layout; this package's files at array speed)
     image_names = sorted(os.listdir(img_dir))
     off, frames, xy, labels = _flatten(trajectories)
